@@ -11,8 +11,17 @@ messages of `--msg-bytes` into a `--region-bytes` HBM region and
 completes them.  Timed region: exactly K steps bracketed by
 barrier + torch.cuda.synchronize on both sides; value is the whole-job
 aggregate GB/s (sum of bytes over all ranks / max elapsed over ranks).
-Payload integrity is proven outside the timed region with the on-GPU
-pattern/CRC kernels.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the result line.  `--full` adds everything else,
+outside the timed region: the payload-integrity proof (on-GPU
+pattern/CRC kernels; a failure exits 2) and the 4 KiB / 1 MiB points
+the metric names (`config.msg_sweep_gbps`).
+
+`--dump-outputs DIR` writes what the last timed step left at the
+receiver (the HBM region for writes, the staging slots for reads) as
+DIR/<name>.npy, float32.  Inputs are a fixed pattern, so two builds run
+with the same arguments can be compared output for output.
 
 Launch (driver contract):
   python bench.py --gpus 1 --steps 20 --warmup 5
@@ -28,6 +37,12 @@ import time
 
 METRIC = ("ib_write_bw GB/s NIC<->GPU-HBM at 4KB/1MB/64MB msg; "
           "1/2/4/8 MI355X aggregate")
+
+# --dump-outputs: payload bytes kept per array (x4 on disk as float32,
+# so one array stays at 32 MiB); larger arrays are sampled in chunks
+_DUMP_BUDGET = 8 << 20
+_DUMP_CHUNK = 4096
+_DUMP_SEED = 0xD0BB5
 
 
 def verbs_ok() -> bool:
@@ -76,7 +91,68 @@ def parse_args():
     p.add_argument("--streams", type=int, default=2)
     p.add_argument("--skip-integrity", action="store_true")
     p.add_argument("--json-out", default="")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need "
+                        "(outside the timed region): the integrity proof "
+                        "and the 4 KiB / 1 MiB message-size points")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the last timed step left at the "
+                        "receiver as DIR/<name>.npy (float32)")
     return p.parse_args()
+
+
+def dump_sample_chunks(nbytes: int):
+    """Which _DUMP_CHUNK-byte chunks of an nbytes array --dump-outputs
+    keeps: None = the whole array (it fits the budget), else a sorted
+    index array that depends only on nbytes (fixed seed), so two runs
+    with the same arguments sample the same bytes."""
+    if nbytes <= _DUMP_BUDGET:
+        return None
+    import numpy as np
+
+    from rocnrdma_amd.utils import pattern
+
+    n_chunks = nbytes // _DUMP_CHUNK
+    want = _DUMP_BUDGET // _DUMP_CHUNK
+    picks = pattern.splitmix64_words(_DUMP_SEED, 0, want) % np.uint64(n_chunks)
+    return np.unique(picks).astype(np.int64)
+
+
+def dump_array(out_dir: str, name: str, buf) -> None:
+    """Write a flat uint8 buffer (numpy array, or torch tensor on any
+    device) as out_dir/name.npy in float32 — shape (nbytes,) when it fits
+    the budget, else (chunks, _DUMP_CHUNK) for the sampled chunks."""
+    import numpy as np
+
+    is_np = isinstance(buf, np.ndarray)
+    flat = buf.reshape(-1)
+    idx = dump_sample_chunks(flat.shape[0])
+    if idx is not None:
+        n_chunks = flat.shape[0] // _DUMP_CHUNK
+        rows = flat[:n_chunks * _DUMP_CHUNK].reshape(n_chunks, _DUMP_CHUNK)
+        if is_np:
+            flat = rows[idx]
+        else:
+            import torch
+
+            flat = rows.index_select(
+                0, torch.from_numpy(idx).to(rows.device))
+    host = flat if is_np else flat.cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), host.astype(np.float32))
+
+
+def dump_outputs(out_dir: str, tp, direction: str, rank: int) -> None:
+    """The arrays a caller of the timed path receives: the destination
+    region after one-sided writes, the staging slots after reads."""
+    suffix = f"_rank{rank}" if rank else ""
+    if direction == "write":
+        dump_array(out_dir, "region" + suffix, tp.region)
+    else:
+        staging = getattr(tp, "staging_flat", None)
+        if staging is None:
+            staging = tp.staging
+        dump_array(out_dir, "staging" + suffix, staging)
 
 
 def main():
@@ -107,6 +183,17 @@ def main():
 
         numa = topology.bind_rank_near_gpu(device.index)
 
+        # the gfx950 extension carries the message engine and the
+        # integrity/CRC kernels: load it before anything is set up, so a
+        # GPU run without it fails here instead of measuring a tree
+        # whose native half is missing
+        import rocnrdma_amd.ops as ops
+
+        if not ops.have_ext():
+            raise SystemExit(
+                "rocnrdma_amd.ops._p2p_ext is not built "
+                "(python __graft_entry__.py build)")
+
     from rocnrdma_amd.transport import get_transport
 
     # fake transport on CPU boxes gets a small region so CI stays fast
@@ -121,6 +208,12 @@ def main():
     msg = min(args.msg_bytes, region)
 
     if tname == "verbs":
+        if args.dump_outputs:
+            # the region lives in the native harness process, which has
+            # no way to hand it back; refuse rather than dump nothing
+            raise SystemExit(
+                "--dump-outputs is not available on the verbs transport "
+                "(use --transport sdma or fake)")
         return run_verbs(args, msg, region, rank, world, has_gpu, device,
                          numa, dist)
 
@@ -179,16 +272,21 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # before the integrity pass, which re-patterns the whole region
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, tp, args.direction, rank)
+
     integrity = "skipped"
-    if not args.skip_integrity:
+    if args.full and not args.skip_integrity:
         bad = tp.integrity_check(seed=0xC0FFEE + rank)
         integrity = "ok" if bad == 0 else f"FAILED:{bad}"
 
-    # the metric names 4KB/1MB/64MB: attach quick per-GPU points for the
-    # other two sizes (outside the timed region; single-rank runs only —
-    # the scaling runs keep the headline size)
+    # --full: the metric names 4KB/1MB/64MB — attach quick per-GPU points
+    # for the other two sizes (outside the timed region; single-rank runs
+    # only — the scaling runs keep the headline size)
     msg_sweep = None
-    if world == 1 and tp.name in ("sdma", "fake") and not args.msgs_per_step:
+    if (args.full and world == 1 and tp.name in ("sdma", "fake")
+            and not args.msgs_per_step):
         from rocnrdma_amd.harness.sweep import run_point
         from rocnrdma_amd.transport import get_transport as _gt
 
@@ -314,7 +412,8 @@ def run_verbs(args, msg, region, rank, world, has_gpu, device, numa, dist):
     rec = run_harness_steps(msg_bytes=msg, region_bytes=region,
                             steps=args.steps, warmup=args.warmup,
                             direction=args.direction, mr=mr,
-                            device_index=dev_idx, seed=0xC0FFEE + rank)
+                            device_index=dev_idx, seed=0xC0FFEE + rank,
+                            integrity=args.full)
     if dist is not None:
         dist.barrier()
 
@@ -329,10 +428,10 @@ def run_verbs(args, msg, region, rank, world, has_gpu, device, numa, dist):
     value = total_bytes / elapsed / 1e9
     integrity = rec.get("integrity", "skipped")
 
-    # metric names 4KB/1MB/64MB: quick per-GPU points outside the
-    # timed region (single-rank runs only, like the sdma path)
+    # --full: metric names 4KB/1MB/64MB — quick per-GPU points outside
+    # the timed region (single-rank runs only, like the sdma path)
     msg_sweep = None
-    if world == 1:
+    if args.full and world == 1:
         msg_sweep = {}
         for other in (4096, 1 << 20):
             if other == msg:

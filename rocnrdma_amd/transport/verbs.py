@@ -68,13 +68,14 @@ def harness_binary() -> str | None:
 def run_harness_steps(*, msg_bytes: int, region_bytes: int, steps: int,
                       warmup: int, direction: str = "write",
                       mr: str = "auto", device_index: int = 0,
-                      seed: int = 0xC0FFEE,
+                      seed: int = 0xC0FFEE, integrity: bool = True,
                       timeout: float = 600.0) -> dict:
     """One native step-mode run (rocp2p_bw --steps): W untimed warmup +
     K timed steps through the REAL verbs data plane (ibv_reg_mr on the
     region per the MR mode, chained RDMA WRITE/READ WRs, CQ drain).
     Returns the harness's JSON record (keys: secs, msgs, gbps,
-    integrity, ...).  Raises RuntimeError with the harness stderr on
+    integrity, ...); integrity=False skips the harness's untimed
+    integrity pass.  Raises RuntimeError with the harness stderr on
     failure."""
     import json as _json
     import subprocess
@@ -89,6 +90,8 @@ def run_harness_steps(*, msg_bytes: int, region_bytes: int, steps: int,
            "--dir", direction, "--steps", str(steps),
            "--warmup", str(warmup), "--device", str(device_index),
            "--seed", str(seed), "--json"]
+    if not integrity:
+        cmd.append("--no-integrity")
     out = subprocess.run(cmd, capture_output=True, text=True,
                          timeout=timeout)
     if out.returncode != 0:

@@ -32,7 +32,7 @@ def _env(extra=None):
 
 @pytest.mark.timeout(600)
 def test_bench_single_rank_gpu():
-    out = subprocess.run([sys.executable, BENCH] + SMALL,
+    out = subprocess.run([sys.executable, BENCH, "--full"] + SMALL,
                          capture_output=True, text=True, env=_env(),
                          cwd=ROOT, timeout=480)
     assert out.returncode == 0, out.stderr
@@ -41,6 +41,43 @@ def test_bench_single_rank_gpu():
     assert r["config"]["transport"] == "sdma"
     assert r["config"]["integrity"] == "ok"
     assert r["value"] > 5  # GB/s; PCIe path
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_the_written_region(tmp_path):
+    """A plain run (no --full) skips the integrity pass and the extra
+    sizes; --dump-outputs holds the HBM region the last step wrote —
+    64 MiB, so a seeded sample of 4 KiB chunks — byte for byte the
+    staged splitmix64 payloads (16 messages of 4 MiB, one slot each)."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from rocnrdma_amd.utils import pattern
+
+    out = subprocess.run(
+        [sys.executable, BENCH, "--dump-outputs", str(tmp_path)] + SMALL,
+        capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=480)
+    assert out.returncode == 0, out.stderr
+    r = json.loads([l for l in out.stdout.splitlines()
+                    if l.startswith("{")][0])
+    assert r["config"]["transport"] == "sdma"
+    assert r["config"]["integrity"] == "skipped"
+    assert r["config"]["msg_sweep_gbps"] is None
+    assert r["steps"] == 3 and r["ms_per_step"] > 0
+    assert r["value"] > 5  # GB/s; PCIe path
+
+    assert os.listdir(tmp_path) == ["region.npy"]
+    got = np.load(tmp_path / "region.npy")
+    idx = bench.dump_sample_chunks(67108864)
+    assert got.dtype == np.float32 and got.shape == (len(idx), 4096)
+    msg = 4194304
+    want = np.empty((len(idx), 4096), dtype=np.uint8)
+    for k, off in enumerate(idx * 4096):
+        slot = off // msg  # 16 messages, 16 staging slots
+        want[k] = pattern.splitmix64_words(
+            0xDA7A, slot * 8192 + (off % msg) // 8, 512).view(np.uint8)
+    assert np.array_equal(got, want.astype(np.float32))
 
 
 @pytest.mark.timeout(600)
@@ -53,7 +90,7 @@ def test_bench_two_ranks_one_gpu():
                     "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1",
                     "MASTER_PORT": "29612"})
         procs.append(subprocess.Popen(
-            [sys.executable, BENCH, "--gpus", "2"] + SMALL,
+            [sys.executable, BENCH, "--gpus", "2", "--full"] + SMALL,
             stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
             env=env, cwd=ROOT))
     outs = [p.communicate(timeout=480) for p in procs]

@@ -99,7 +99,8 @@ def test_bench_verbs_peer_mr_shape_on_gpu(built):
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
          "--steps", "2", "--warmup", "1", "--msg-bytes", "1048576",
-         "--region-bytes", "16777216", "--verbs-mr", "dmabuf"],
+         "--region-bytes", "16777216", "--verbs-mr", "dmabuf",
+         "--full"],
         capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     # dmabuf MR mode: must SUCCEED end to end on real VRAM
     assert out.returncode == 0, out.stdout + out.stderr

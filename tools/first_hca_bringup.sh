@@ -65,7 +65,7 @@ for c in 1 2 4 8 16 32 64; do
 done
 
 step "6. the metric (bench contract; auto now selects verbs)"
-run python3 "$HERE/bench.py" --gpus 1 --steps 20 --warmup 5
+run python3 "$HERE/bench.py" --gpus 1 --steps 20 --warmup 5 --full
 
 step "DONE"
 echo "Compare step-6 output against profiles/ (PCIe envelope 50-57"

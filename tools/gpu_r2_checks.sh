@@ -18,7 +18,7 @@ echo "=== pytest -m gpu ==="
 timeout 600 python -m pytest tests -m gpu -x -q 2>&1 | tail -8
 
 echo "=== bench.py sanity (auto -> sdma on this box) ==="
-timeout 300 python bench.py --gpus 1 --steps 10 --warmup 3 \
+timeout 300 python bench.py --gpus 1 --steps 10 --warmup 3 --full \
     --json-out gpurun_out/r2/bench_n1.json | tail -2
 
 echo "=== dmabuf MR end-to-end on real VRAM (fakeverbs mmaps the fd) ==="

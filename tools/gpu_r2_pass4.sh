@@ -14,7 +14,7 @@ ROCNR_FORCE_VERBS=1 \
 ROCNR_VERBS_HARNESS=$PWD/harness/build/rocp2p_bw_fakeverbs \
 timeout 300 python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29751 \
-    bench.py --gpus 2 --steps 5 --warmup 2 --msg-bytes 1048576 \
+    bench.py --gpus 2 --steps 5 --warmup 2 --msg-bytes 1048576 --full \
     --region-bytes 67108864 --verbs-mr dmabuf \
     --json-out gpurun_out/r2/bench_verbs_2rank.json 2>&1 | tail -2
 
