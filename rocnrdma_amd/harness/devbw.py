@@ -35,6 +35,12 @@ def bench_kernels(nbytes: int, iters: int = 10) -> dict:
     out["fill_GBps"] = timeit(lambda: ops.fill_(buf, 1), nbytes)
     out["verify_GBps"] = timeit(lambda: ops.verify(buf, 1), nbytes)
     out["crc32_GBps"] = timeit(lambda: ops.crc32_pages(buf), nbytes)
+    # digests: 1 MiB messages without a sync; the whole region through
+    # the public call, 4-byte readback included
+    msg = 1 << 20 if nbytes % (1 << 20) == 0 else nbytes
+    out["crc32_msgs_GBps"] = timeit(lambda: ops.crc32_messages(buf, msg),
+                                    nbytes)
+    out["crc32_region_GBps"] = timeit(lambda: ops.crc32(buf), nbytes)
     out["copy_GBps_rw"] = timeit(lambda: ops.copy_(dst, buf), 2 * nbytes)
     out["copy_nt_GBps_rw"] = timeit(lambda: ops.copy_nt_(dst, buf),
                                     2 * nbytes)

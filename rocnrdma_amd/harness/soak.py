@@ -4,6 +4,7 @@ stability tier for production deployment (run for minutes/hours on a
 deploy candidate; the GPU test tier runs a short bounded pass).
 
 CLI: python -m rocnrdma_amd.harness.soak [--secs 30] [--transport auto]
+                                         [--audit pattern|crc]
 Exit nonzero on any integrity failure.
 """
 from __future__ import annotations
@@ -17,8 +18,14 @@ SIZES = [4 << 10, 16 << 10, 64 << 10, 256 << 10, 1 << 20, 4 << 20]
 
 def run_soak(transport: str = "auto", secs: float = 10.0,
              region_bytes: int = 256 << 20, seed: int = 1234,
-             device=None, metrics=None) -> dict:
+             device=None, metrics=None, audit: str = "pattern") -> dict:
+    """audit="pattern": splitmix64 pattern + integrity_check (default).
+    audit="crc": a seeded random payload per cycle through digest_check
+    (per-message CRC32, content-independent)."""
     from rocnrdma_amd.transport import get_transport
+
+    if audit not in ("pattern", "crc"):
+        raise ValueError(f"audit must be 'pattern' or 'crc', not {audit!r}")
 
     if metrics is None:
         from rocnrdma_amd.utils.metrics import TransferMetrics
@@ -42,8 +49,16 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
                 tp.post_many(posted, burst)
                 posted += burst
                 tp.flush()
-            # audit: full-region pattern transfer + receiver verify
-            bad = tp.integrity_check(seed=rng.getrandbits(32))
+            # audit: full-region transfer + receiver verify
+            if audit == "crc":
+                import numpy as np
+
+                payload = np.random.default_rng(
+                    rng.getrandbits(32)).integers(
+                        0, 256, region, dtype=np.uint8)
+                bad = tp.digest_check(payload)
+            else:
+                bad = tp.integrity_check(seed=rng.getrandbits(32))
             stats["audits"] += 1
             if bad:
                 stats["failures"] += 1
@@ -65,6 +80,10 @@ def main():
     ap.add_argument("--transport", default="auto")
     ap.add_argument("--region-bytes", type=int, default=256 << 20)
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--audit", choices=["pattern", "crc"],
+                    default="pattern",
+                    help="pattern: splitmix64 + verify; crc: random "
+                         "payload + per-message CRC32 digests")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="expose Prometheus metrics on this port")
     args = ap.parse_args()
@@ -72,7 +91,7 @@ def main():
 
     metrics = TransferMetrics(port=args.metrics_port or None)
     stats = run_soak(args.transport, args.secs, args.region_bytes,
-                     args.seed, metrics=metrics)
+                     args.seed, metrics=metrics, audit=args.audit)
     print(stats)
     raise SystemExit(1 if stats["failures"] else 0)
 

@@ -43,6 +43,26 @@ def crc32_pages(buf: torch.Tensor) -> torch.Tensor:
     return _require().crc32_pages(buf)
 
 
+def crc32_messages(region: torch.Tensor, msg_bytes: int,
+                   offs: torch.Tensor | None = None, *,
+                   grid_cap: int = 0) -> torch.Tensor:
+    """zlib-compatible CRC32 of each msg_bytes message; int32 tensor[n] on
+    GPU, no sync (view as uint32 for zlib's values).
+
+    Without offs the region is n = nbytes // msg_bytes back-to-back
+    messages; with offs (contiguous int64 GPU tensor, 16-byte-aligned byte
+    offsets as for gather_) message m starts at offs[m].  msg_bytes is a
+    non-zero multiple of 16.  grid_cap caps the workgroup count (0 = tuned
+    default) — a tuning and testing knob."""
+    return _require().crc32_messages(region, msg_bytes, offs, grid_cap)
+
+
+def crc32(buf: torch.Tensor, *, grid_cap: int = 0) -> int:
+    """zlib.crc32 of the whole buffer (any byte length, 16-byte-aligned
+    base), computed in HBM; only the 4-byte digest crosses to the host."""
+    return _require().crc32(buf, grid_cap)
+
+
 def copy_(dst: torch.Tensor, src: torch.Tensor) -> None:
     """Streaming 16 B/lane device copy (bandwidth ceiling probe)."""
     _require().copy_(dst, src)

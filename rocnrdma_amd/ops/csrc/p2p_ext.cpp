@@ -64,6 +64,74 @@ void check_u64_dev(const torch::Tensor& t, const char* who) {
               who, ": descriptor tensor must be contiguous int64 on GPU");
 }
 
+void check_align16(const torch::Tensor& t, const char* who) {
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, who,
+              ": base address must be 16-byte aligned");
+}
+
+// Caller-owned scratch for the digest launchers, from the caching
+// allocator on the current stream (0 bytes for the fused kernel).
+torch::Tensor digest_scratch(const torch::Tensor& like, uint64_t msg_bytes,
+                             uint32_t n) {
+  uint64_t bytes = rocp2p_crc32_msgs_scratch_bytes(msg_bytes, n);
+  return torch::empty({(int64_t)bytes},
+                      torch::dtype(torch::kUInt8).device(like.device()));
+}
+
+torch::Tensor crc32_messages(torch::Tensor region, int64_t msg_bytes,
+                             c10::optional<torch::Tensor> offs,
+                             int64_t grid_cap) {
+  check_buf(region, "crc32_messages");
+  check_align16(region, "crc32_messages");
+  TORCH_CHECK(msg_bytes > 0 && msg_bytes % 16 == 0,
+              "crc32_messages: msg_bytes must be a non-zero multiple of 16");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= 0xffffffffLL,
+              "crc32_messages: grid_cap out of range");
+  uint64_t nbytes = nbytes_of(region);
+  int64_t n;
+  const uint64_t* d_offs = nullptr;
+  if (offs.has_value()) {
+    check_u64_dev(*offs, "crc32_messages");
+    TORCH_CHECK(offs->device() == region.device(),
+                "crc32_messages: offs must live on the region's device");
+    n = offs->numel();
+    d_offs = (const uint64_t*)offs->data_ptr<int64_t>();
+  } else {
+    TORCH_CHECK(nbytes % (uint64_t)msg_bytes == 0,
+                "crc32_messages: region length must be a multiple of "
+                "msg_bytes");
+    n = (int64_t)(nbytes / (uint64_t)msg_bytes);
+  }
+  TORCH_CHECK(n < (1LL << 32), "crc32_messages: too many messages");
+  auto out =
+      torch::empty({n}, torch::dtype(torch::kInt32).device(region.device()));
+  if (!n) return out;
+  auto scratch = digest_scratch(region, (uint64_t)msg_bytes, (uint32_t)n);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  HIP_OK(rocp2p_crc32_msgs(region.data_ptr(), d_offs, (uint64_t)msg_bytes,
+                           (uint32_t)n, (uint32_t*)out.data_ptr<int32_t>(),
+                           scratch.data_ptr(), (uint32_t)grid_cap,
+                           stream.stream()));
+  return out;
+}
+
+int64_t crc32(torch::Tensor buf, int64_t grid_cap) {
+  check_buf(buf, "crc32");
+  check_align16(buf, "crc32");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= 0xffffffffLL,
+              "crc32: grid_cap out of range");
+  uint64_t nbytes = nbytes_of(buf);
+  auto out =
+      torch::empty({1}, torch::dtype(torch::kInt32).device(buf.device()));
+  auto scratch = digest_scratch(buf, nbytes, 1);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  HIP_OK(rocp2p_crc32_region(buf.data_ptr(), nbytes,
+                             (uint32_t*)out.data_ptr<int32_t>(),
+                             scratch.data_ptr(), (uint32_t)grid_cap,
+                             stream.stream()));
+  return (int64_t)(uint32_t)out.item<int32_t>();
+}
+
 void gather_(torch::Tensor region, torch::Tensor dst_offs,
              torch::Tensor src_addrs, int64_t msg_bytes) {
   check_buf(region, "gather_");
@@ -128,11 +196,17 @@ int64_t dmabuf_fd(torch::Tensor buf) {
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.doc() = "MI355X payload kernels: splitmix64 fill / verify, per-page "
-            "CRC32, streaming copy";
+  m.doc() = "MI355X payload kernels: splitmix64 fill / verify, per-page, "
+            "per-message and whole-region CRC32, streaming copy";
   m.def("fill_", &fill_, "in-place splitmix64 pattern fill");
   m.def("verify", &verify, "count words deviating from the pattern");
   m.def("crc32_pages", &crc32_pages, "zlib CRC32 of each 4 KiB page");
+  m.def("crc32_messages", &crc32_messages,
+        "zlib CRC32 of each msg_bytes message (optionally at offs)",
+        py::arg("region"), py::arg("msg_bytes"),
+        py::arg("offs") = py::none(), py::arg("grid_cap") = 0);
+  m.def("crc32", &crc32, "zlib CRC32 of a whole buffer, any byte length",
+        py::arg("buf"), py::arg("grid_cap") = 0);
   m.def("copy_", &copy_, "streaming device copy dst <- src");
   m.def("copy_nt_", &copy_nt_, "nontemporal streaming device copy");
   m.def("gather_", &gather_,

@@ -6,8 +6,8 @@
 
 extern "C" {
 
-// One-time: upload CRC32 slice-by-8 tables + GF(2) shift matrices to
-// device constant memory.  Idempotent, cheap.
+// One-time: upload CRC32 slice-by-8 tables, GF(2) shift matrices and the
+// byte-sliced x^(8n) power table to device constant memory.  Idempotent, cheap.
 hipError_t rocp2p_crc32_init();
 
 // buf[i] = splitmix64(seed + (i+1)*GOLDEN) for each 8-byte word.
@@ -26,6 +26,33 @@ hipError_t rocp2p_verify(const void* buf, uint64_t nbytes, uint64_t seed,
 // lookup tables staged in LDS.
 hipError_t rocp2p_crc32_pages(const void* buf, uint64_t npages,
                               uint32_t* d_out, hipStream_t stream);
+
+// CRC32 digests of caller-supplied payloads, computed in HBM (GF(2)
+// helpers: p2p_crc.h).  Stream-ordered, allocate nothing; d_out is
+// zeroed on `stream` and accumulated with atomicXor (order-independent,
+// so bit-reproducible).
+//
+// msgs: d_out[m] = zlib crc32 of base[off_m, off_m + msg_bytes), off_m =
+// d_offs[m] or m * msg_bytes when d_offs is null.  Same preconditions
+// as rocp2p_gather: msg_bytes a non-zero multiple of 16, base and every
+// offset 16-byte aligned (host-visible violations: hipErrorInvalidValue).
+// region: one digest of any byte length (0 -> 0); buf 16-byte aligned;
+// never loads a byte at or beyond buf + nbytes.
+// d_scratch: rocp2p_crc32_msgs_scratch_bytes() bytes (region: query with
+// (nbytes, 1)); the fused kernel needs none, the query returns 0 and
+// null is accepted.
+// grid_cap: 0 = tuned default; otherwise the maximum number of
+// workgroups (16 waves each).  A tuning and testing knob: it makes each
+// wave walk a multi-chunk run at test-sized inputs (the default grid
+// only does so above 16 MiB).
+hipError_t rocp2p_crc32_msgs(const void* base, const uint64_t* d_offs,
+                             uint64_t msg_bytes, uint32_t n, uint32_t* d_out,
+                             void* d_scratch, uint32_t grid_cap,
+                             hipStream_t stream);
+uint64_t rocp2p_crc32_msgs_scratch_bytes(uint64_t msg_bytes, uint32_t n);
+hipError_t rocp2p_crc32_region(const void* buf, uint64_t nbytes,
+                               uint32_t* d_out, void* d_scratch,
+                               uint32_t grid_cap, hipStream_t stream);
 
 // Streaming device copy (bandwidth ceiling probe), 16 B/lane.
 hipError_t rocp2p_copy(void* dst, const void* src, uint64_t nbytes,

@@ -27,6 +27,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include "p2p_kernels.h"
+#include "p2p_crc.h"
 #include "p2p_pattern.h"
 
 #define WAVE 64u
@@ -317,6 +318,252 @@ __global__ void __launch_bounds__(256) k_crc32_pages(
 }
 
 // ---------------------------------------------------------------------
+// CRC32 digests per message / per region (zlib-exact, any content).
+//
+// Every message is cut into 4 KiB chunks from its own start plus at
+// most one partial chunk; chunks are numbered message-major and each
+// WAVE owns a contiguous run of them (run length chosen by the
+// launcher).  Full chunks reuse the page scheme above (slice-by-8 +
+// uniform log tree, same LDS tables, same 32 KB per workgroup).
+// Inside a run the wave carries acc = crc(chunks so far of this
+// message): acc = shift(acc, 4096) ^ crc(chunk), the 4 KiB shift being
+// the level-5 (2 KiB) operator applied twice — 8 LDS lookups, no extra
+// table.  When the message or the run ends, acc still has r bytes of
+// the message after it and contributes shift(acc, r) to the digest.
+// That one variable shift is spread over the wave: lane j < 8 fetches
+// x^(8 * byte_j(r) * 256^j) from a byte-sliced power table (8 KiB,
+// constant memory), a __shfl_xor product tree over only the levels r
+// needs yields x^(8r) in lane 0, one more mulmod applies it — 2
+// mulmods per flush below 64 KiB remaining, 3 below 4 GiB, all VALU
+// while the kernel is LDS-bound.
+// Contributions are XORed into d_out[m] with atomicXor (launcher zeroes
+// it); XOR is order-independent so digests are bit-reproducible.  Shares
+// of runs that end inside a message are first XORed across the
+// workgroup, whose waves own adjacent runs.
+//
+// The partial chunk (valid < 4096 bytes, any byte count) uses the flat
+// identity: lane l owns [64l, min(64l+64, valid)), lanes past the end
+// contribute 0, each lane shifts its own CRC by valid - end_l and the
+// wave XOR-reduces.  No byte at or beyond the message end is loaded:
+// the last partial 16 bytes are fetched with 8/4/2/1-byte loads.
+
+__constant__ uint32_t c_xpow8[8][256];  // x^(8 * v * 256^j) mod P
+
+typedef uint32_t crc_tab256[256];
+
+__device__ __forceinline__ uint32_t crc_step8(const crc_tab256* t,
+                                              uint32_t crc, uint32_t lo,
+                                              uint32_t hi) {
+  uint32_t a = lo ^ crc;
+  return t[7][a & 0xff] ^ t[6][(a >> 8) & 0xff] ^ t[5][(a >> 16) & 0xff] ^
+         t[4][a >> 24] ^ t[3][hi & 0xff] ^ t[2][(hi >> 8) & 0xff] ^
+         t[1][(hi >> 16) & 0xff] ^ t[0][hi >> 24];
+}
+
+// byte-sliced GF(2) operator applied to c (4 lookups)
+__device__ __forceinline__ uint32_t crc_apply(const crc_tab256* m,
+                                              uint32_t c) {
+  return m[0][c & 0xff] ^ m[1][(c >> 8) & 0xff] ^ m[2][(c >> 16) & 0xff] ^
+         m[3][c >> 24];
+}
+
+// x^(8*r) in lane 0 (r uniform; other lanes hold partial products).
+__device__ __forceinline__ uint32_t crc_xpow_wave(uint64_t r, uint32_t lane) {
+  const uint32_t j = lane & 7;  // lanes 8.. mirror 0..7
+  uint32_t t = c_xpow8[j][(r >> (8 * j)) & 0xff];
+  // level k folds bytes 2^k apart: needed once r has a byte 2^k or above
+#pragma unroll
+  for (int k = 0; k < 3; k++)
+    if (r >> (8u << k))
+      t = rocp2p_crc_mulmod(t, __shfl_xor(t, 1u << k, WAVE));
+  return t;
+}
+
+// Load the nb (0..64) bytes of a lane's segment into w[16], zero padded.
+__device__ __forceinline__ void crc_load_partial(const uint8_t* seg,
+                                                 uint32_t nb,
+                                                 uint32_t w[16]) {
+#pragma unroll
+  for (uint32_t q = 0; q < 4; q++) {
+    const uint8_t* p = seg + 16 * q;
+    uint64_t lo = 0, hi = 0;
+    if (nb >= 16 * q + 16) {
+      uint4 v = *reinterpret_cast<const uint4*>(p);
+      lo = v.x | ((uint64_t)v.y << 32);
+      hi = v.z | ((uint64_t)v.w << 32);
+    } else if (nb > 16 * q) {
+      uint32_t rem = nb - 16 * q;  // 1..15: naturally aligned narrow loads
+      uint64_t first = 0, rest = 0;
+      uint32_t sh = 0;
+      if (rem & 8) { first = *reinterpret_cast<const uint64_t*>(p); p += 8; }
+      if (rem & 4) { rest = *reinterpret_cast<const uint32_t*>(p); p += 4; sh = 32; }
+      if (rem & 2) {
+        rest |= (uint64_t)*reinterpret_cast<const uint16_t*>(p) << sh;
+        p += 2;
+        sh += 16;
+      }
+      if (rem & 1) rest |= (uint64_t)*p << sh;
+      if (rem & 8) { lo = first; hi = rest; } else { lo = rest; }
+    }
+    w[4 * q] = (uint32_t)lo;
+    w[4 * q + 1] = (uint32_t)(lo >> 32);
+    w[4 * q + 2] = (uint32_t)hi;
+    w[4 * q + 3] = (uint32_t)(hi >> 32);
+  }
+}
+
+// zlib crc32 of the first nb (0..64) bytes held in w[16]
+__device__ __forceinline__ uint32_t crc_bytes64(const crc_tab256* t,
+                                                const uint32_t w[16],
+                                                uint32_t nb) {
+  uint32_t crc = 0xFFFFFFFFu;
+  const uint32_t n8 = nb >> 3, rem = nb & 7;
+#pragma unroll
+  for (uint32_t i = 0; i < 8; i++)
+    if (i < n8) crc = crc_step8(t, crc, w[2 * i], w[2 * i + 1]);
+  if (rem) {
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 8; i++)
+      if (i == n8) { lo = w[2 * i]; hi = w[2 * i + 1]; }
+    uint64_t v = lo | ((uint64_t)hi << 32);
+    for (uint32_t j = 0; j < rem; j++, v >>= 8)
+      crc = t[0][(crc ^ (uint32_t)v) & 0xff] ^ (crc >> 8);
+  }
+  return crc ^ 0xFFFFFFFFu;
+}
+
+// One wave per run of `run` consecutive chunks; CRC_DIGEST_WAVES waves
+// per workgroup share one copy of the tables.
+// Message m starts at base + (offs ? offs[m] : m * msg_bytes); cpm =
+// chunks per message = ceil(msg_bytes / 4096); total = n * cpm.
+#define CRC_DIGEST_WAVES 16u
+__global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
+    const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
+    uint64_t msg_bytes, uint64_t cpm, uint64_t total, uint64_t run,
+    uint32_t* __restrict__ out) {
+  __shared__ uint32_t s_tab[8][256];
+  __shared__ uint32_t s_stab[6][4][256];
+
+  for (uint32_t i = threadIdx.x; i < 8 * 256; i += blockDim.x)
+    (&s_tab[0][0])[i] = (&c_crc_tab[0][0])[i];
+  for (uint32_t i = threadIdx.x; i < 6 * 4 * 256; i += blockDim.x)
+    (&s_stab[0][0][0])[i] = (&c_shift_tab[0][0][0])[i];
+  __syncthreads();
+
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv = threadIdx.x / WAVE, nwv = blockDim.x / WAVE;
+  const uint64_t wave = (uint64_t)blockIdx.x * nwv + wv;
+  uint64_t c0 = wave * run;
+  if (c0 > total) c0 = total;  // idle wave: empty run, still joins the merge
+  const uint64_t c1 = (total - c0 < run) ? total : c0 + run;
+
+  uint64_t m = 0, ci = 0;
+  const uint8_t* mp = base;
+  if (c0 < c1) {
+    m = c0 / cpm;
+    ci = c0 - m * cpm;
+    mp = base + (offs ? offs[m] : m * msg_bytes);
+  }
+  uint32_t acc = 0;  // crc of this run's full chunks of message m so far
+  // contribution of a run that ends inside a message: merged with the
+  // workgroup's other waves below (0 contributes nothing)
+  uint32_t pend_f = 0, pend_m = 0;
+
+  for (uint64_t c = c0; c < c1; c++) {
+    const uint64_t pos = ci * PAGE;
+    const uint64_t left = msg_bytes - pos;  // > 0
+    const uint8_t* seg = mp + pos + lane * SEG;
+    uint64_t done;  // message bytes [.., done) are covered by acc
+    if (left >= PAGE) {
+      uint4 v0 = reinterpret_cast<const uint4*>(seg)[0];
+      uint4 v1 = reinterpret_cast<const uint4*>(seg)[1];
+      uint4 v2 = reinterpret_cast<const uint4*>(seg)[2];
+      uint4 v3 = reinterpret_cast<const uint4*>(seg)[3];
+      uint32_t w[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w,
+                        v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
+      uint32_t crc = 0xFFFFFFFFu;
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+        crc = crc_step8(s_tab, crc, w[2 * i], w[2 * i + 1]);
+      crc ^= 0xFFFFFFFFu;
+      // uniform log tree, as in k_crc32_pages
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        uint32_t partner = __shfl_xor(crc, 1u << k, WAVE);
+        bool is_left = ((lane >> k) & 1u) == 0;
+        uint32_t cl = is_left ? crc : partner;
+        uint32_t cr = is_left ? partner : crc;
+        crc = crc_apply(s_stab[k], cl) ^ cr;
+      }
+      acc = crc_apply(s_stab[5], crc_apply(s_stab[5], acc)) ^ crc;
+      done = pos + PAGE;
+    } else {
+      const uint32_t valid = (uint32_t)left;  // 1..4095
+      const uint32_t beg = lane * SEG;
+      const uint32_t nb = valid > beg ? min(valid - beg, SEG) : 0u;
+      uint32_t w[16];
+      crc_load_partial(seg, nb, w);
+      uint32_t x = 0;
+      if (nb)
+        x = rocp2p_crc_mulmod(
+            rocp2p_crc_xpow8(valid - (beg + nb), c_xpow8),
+            crc_bytes64(s_tab, w, nb));
+      for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
+      if (lane == 0) atomicXor(&out[m], x);
+      done = pos;  // acc (if any) still has `valid` bytes after it
+    }
+    const bool msg_end = ci + 1 == cpm;
+    if (msg_end || c + 1 == c1) {
+      if (acc) {  // a zero CRC contributes nothing wherever it sits
+        const uint64_t r = msg_bytes - done;
+        uint32_t f = acc;
+        if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
+        if (msg_end) {
+          if (lane == 0) atomicXor(&out[m], f);
+        } else {
+          pend_f = f;
+          pend_m = (uint32_t)m;
+        }
+      }
+      acc = 0;
+    }
+    if (msg_end) {
+      m++;
+      ci = 0;
+      if (c + 1 < c1) mp = base + (offs ? offs[m] : m * msg_bytes);
+    } else {
+      ci++;
+    }
+  }
+
+  // Adjacent waves own adjacent runs, so in a long message the whole
+  // workgroup's pending shares target one digest: XOR them here and
+  // issue one atomic instead of one per wave (same-line atomics
+  // serialize in L2).  The tables are dead after the barrier; their
+  // first words carry the hand-off.
+  __syncthreads();
+  uint32_t* s_pend = &s_tab[0][0];
+  if (lane == 0) {
+    s_pend[2 * wv] = pend_f;
+    s_pend[2 * wv + 1] = pend_m;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t f = s_pend[0], fm = s_pend[1];
+    for (uint32_t w = 1; w < nwv; w++) {
+      if (s_pend[2 * w + 1] != fm) {
+        if (f) atomicXor(&out[fm], f);
+        f = 0;
+        fm = s_pend[2 * w + 1];
+      }
+      f ^= s_pend[2 * w];
+    }
+    if (f) atomicXor(&out[fm], f);
+  }
+}
+
+// ---------------------------------------------------------------------
 // launchers
 
 static inline uint32_t stream_grid(uint64_t items, uint32_t per_block) {
@@ -434,6 +681,12 @@ extern "C" hipError_t rocp2p_crc32_init() {
   if (e != hipSuccess) return e;
   e = hipMemcpyToSymbol(HIP_SYMBOL(c_shift_tab), stab, sizeof(stab));
   if (e != hipSuccess) return e;
+  static uint32_t xtab[ROCP2P_CRC_XPOW_N];
+  rocp2p_crc_xpow_table(xtab);
+  static uint32_t xtab8[8][256];
+  rocp2p_crc_xpow8_table(xtab8, xtab);
+  e = hipMemcpyToSymbol(HIP_SYMBOL(c_xpow8), xtab8, sizeof(xtab8));
+  if (e != hipSuccess) return e;
   g_crc_ready = true;
   return hipSuccess;
 }
@@ -448,4 +701,70 @@ extern "C" hipError_t rocp2p_crc32_pages(const void* buf, uint64_t npages,
   hipLaunchKernelGGL(k_crc32_pages, dim3((uint32_t)blocks), dim3(256), 0,
                      stream, (const uint32_t*)buf, npages, d_out);
   return hipGetLastError();
+}
+
+// Digest launch shape (measured on MI355X): one chunk per wave up to
+// 256 workgroups of 16 waves = 4096 waves = 16 per CU, which already
+// saturates the LDS; beyond 16 MiB the grid stays and the runs lengthen,
+// so flushes get rarer as the input grows (1 GiB of 1 MiB messages:
+// 3.1 TB/s with 8-chunk runs, 3.9 TB/s with 64-chunk runs).  16-wave
+// workgroups beat 4- and 8-wave ones by 2-15% from 64 MiB up: one table
+// copy per CU and 16 pending shares merged into one atomic.
+// grid_cap != 0 caps the workgroup count instead of 256.
+static hipError_t crc32_digest_launch(const void* base,
+                                      const uint64_t* d_offs,
+                                      uint64_t msg_bytes, uint32_t n,
+                                      uint32_t* d_out, uint32_t grid_cap,
+                                      hipStream_t stream) {
+  hipError_t e = rocp2p_crc32_init();
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+  if (e != hipSuccess) return e;
+  if (!msg_bytes) return hipSuccess;  // crc32 of nothing is 0
+  uint64_t cpm = msg_bytes / PAGE + (msg_bytes % PAGE != 0);
+  uint64_t total;
+  if (__builtin_mul_overflow(cpm, (uint64_t)n, &total))
+    return hipErrorInvalidValue;
+  const uint64_t W = CRC_DIGEST_WAVES;
+  uint64_t cap = grid_cap ? grid_cap : 256;
+  uint64_t blocks = (total + W - 1) / W;
+  if (blocks > cap) blocks = cap;
+  uint64_t run = (total + W * blocks - 1) / (W * blocks);
+  hipLaunchKernelGGL(k_crc32_msgs, dim3((uint32_t)blocks),
+                     dim3(WAVE * CRC_DIGEST_WAVES), 0,
+                     stream, (const uint8_t*)base, d_offs, msg_bytes, cpm,
+                     total, run, d_out);
+  return hipGetLastError();
+}
+
+// Fused design: chunk CRCs never leave the wave, so no scratch.
+extern "C" uint64_t rocp2p_crc32_msgs_scratch_bytes(uint64_t msg_bytes,
+                                                    uint32_t n) {
+  (void)msg_bytes;
+  (void)n;
+  return 0;
+}
+
+extern "C" hipError_t rocp2p_crc32_msgs(const void* base,
+                                        const uint64_t* d_offs,
+                                        uint64_t msg_bytes, uint32_t n,
+                                        uint32_t* d_out, void* d_scratch,
+                                        uint32_t grid_cap,
+                                        hipStream_t stream) {
+  (void)d_scratch;
+  if (msg_bytes % 16 || !msg_bytes || (uintptr_t)base % 16)
+    return hipErrorInvalidValue;
+  if (!n) return hipSuccess;
+  return crc32_digest_launch(base, d_offs, msg_bytes, n, d_out, grid_cap,
+                             stream);
+}
+
+extern "C" hipError_t rocp2p_crc32_region(const void* buf, uint64_t nbytes,
+                                          uint32_t* d_out, void* d_scratch,
+                                          uint32_t grid_cap,
+                                          hipStream_t stream) {
+  (void)d_scratch;
+  if ((uintptr_t)buf % 16) return hipErrorInvalidValue;
+  return crc32_digest_launch(buf, nullptr, nbytes, 1, d_out, grid_cap,
+                             stream);
 }

@@ -10,7 +10,9 @@ the roles flip (region -> staging), mirroring RDMA READ.
 `integrity_check()` proves the data path end to end: it moves the whole
 region with deterministic per-message payloads and verifies the receiving
 side (on-GPU via the CRC/verify kernels when the receiver is HBM) —
-never inside a timed section.
+never inside a timed section.  `digest_check(payload)` does the same for
+caller-supplied content: per-message CRC32 digests taken at the sender
+and at the receiver are compared, like a NIC's per-message ICRC.
 """
 from __future__ import annotations
 
@@ -53,6 +55,25 @@ class Transport(abc.ABC):
     def integrity_check(self, seed: int) -> int:
         """Move the whole region with pattern payloads; return mismatching
         8-byte words at the receiver (0 = intact)."""
+
+    def digest_check(self, payload) -> int:
+        """Payload-agnostic check: move the whole region carrying
+        `payload` (any uint8 array of region_bytes, arbitrary content) in
+        the same bursts as integrity_check; return the number of MESSAGES
+        whose receiver CRC32 digest differs from the sender's (0 =
+        intact).  Optional: backends without it raise."""
+        raise NotImplementedError(
+            f"{self.name} transport does not implement digest_check")
+
+    def _payload_bytes(self, payload):
+        """payload as a flat contiguous uint8 numpy array of region_bytes."""
+        import numpy as np
+
+        arr = np.ascontiguousarray(payload)
+        if arr.dtype != np.uint8 or arr.size != self.region_bytes:
+            raise ValueError(
+                f"payload must be uint8 of {self.region_bytes} bytes")
+        return arr.reshape(-1)
 
     def close(self) -> None:  # optional
         pass

@@ -3,6 +3,8 @@ ib_write_bw loopback") without hardware.  Used by the CPU test tier and
 as the bench fallback where no GPU/HCA exists."""
 from __future__ import annotations
 
+import zlib
+
 import numpy as np
 
 from ..utils import pattern
@@ -52,4 +54,28 @@ class FakeTransport(Transport):
                 np.count_nonzero(
                     self.staging[i % self.inflight].view(np.uint64)
                     != ref[off : off + self.msg_bytes].view(np.uint64)))
+        return bad
+
+    def digest_check(self, payload) -> int:
+        pay = self._payload_bytes(payload)
+        n, msg = self.msgs_per_region, self.msg_bytes
+        if self.direction == "write":
+            sent = []
+            for i in range(n):
+                slot = self.staging[i % self.inflight]
+                slot[:] = pay[i * msg : (i + 1) * msg]
+                sent.append(zlib.crc32(slot.tobytes()))
+                self.post(i)
+            self.flush()
+            got = pattern.crc32_messages_reference(self.region, msg)
+            return int(np.count_nonzero(got != np.array(sent, np.uint32)))
+        # read: load the region, digest it, pull slot by slot
+        self.region[:] = pay
+        sent = pattern.crc32_messages_reference(self.region, msg)
+        bad = 0
+        for i in range(n):
+            self.post(i)
+            self.flush()
+            got = zlib.crc32(self.staging[i % self.inflight].tobytes())
+            bad += int(got != int(sent[i]))
         return bad

@@ -180,5 +180,51 @@ class SdmaTransport(Transport):
             i += burst
         return bad
 
+    def digest_check(self, payload) -> int:
+        """Per-message CRC32 of arbitrary content, sender vs receiver.
+        The HBM side is digested by one crc32_messages launch, so only
+        4 bytes per message ever cross back — no payload readback."""
+        import zlib
+
+        import numpy as np
+
+        from .. import ops
+
+        pay = self._payload_bytes(payload)
+        pay_t = torch.from_numpy(pay)
+        n, msg = self.msgs_per_region, self.msg_bytes
+        if self.direction == "write":
+            sent = np.empty(n, dtype=np.uint32)
+            i = 0
+            while i < n:
+                burst = min(self.inflight, n - i)
+                for j in range(i, i + burst):
+                    slot = self.staging[j % self.inflight]
+                    slot.copy_(pay_t[j * msg:(j + 1) * msg])
+                    sent[j] = zlib.crc32(slot.numpy())
+                    self.post(j)
+                self.flush()  # slots reused next burst: must complete
+                i += burst
+            got = ops.crc32_messages(self.region, msg)
+            return int(np.count_nonzero(
+                got.cpu().numpy().view(np.uint32) != sent))
+        # read: load HBM with the payload, digest it there, pull to host
+        self.region.copy_(pay_t)
+        sent = ops.crc32_messages(self.region, msg)
+        torch.cuda.synchronize(self.device)
+        sent = sent.cpu().numpy().view(np.uint32)
+        bad = 0
+        i = 0
+        while i < n:
+            burst = min(self.inflight, n - i)
+            for j in range(i, i + burst):
+                self.post(j)
+            self.flush()
+            for j in range(i, i + burst):
+                got = zlib.crc32(self.staging[j % self.inflight].numpy())
+                bad += int(got != int(sent[j]))
+            i += burst
+        return bad
+
     def close(self) -> None:
         self.flush()

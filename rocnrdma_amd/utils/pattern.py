@@ -41,3 +41,66 @@ def crc32_pages_reference(data: bytes | np.ndarray) -> np.ndarray:
         [zlib.crc32(buf[i : i + PAGE]) for i in range(0, len(buf), PAGE)],
         dtype=np.uint32,
     )
+
+
+# -- CRC32 digest algebra (mirrors rocnrdma_amd/ops/csrc/p2p_crc.h) ----
+# Polynomials are 32-bit, reflected (bit 31 = x^0), mod P = 0xEDB88320.
+# zlib.crc32 exists in Python but zlib's crc32_combine is not exposed.
+_CRC_POLY = 0xEDB88320
+_CRC_ONE = 0x80000000
+
+
+def _crc_mulmod(a: int, b: int) -> int:
+    """a * b mod P."""
+    p = 0
+    for i in range(31, -1, -1):
+        if (a >> i) & 1:
+            p ^= b
+        b = (b >> 1) ^ (_CRC_POLY if b & 1 else 0)
+    return p
+
+
+def _crc_xpow_table() -> list[int]:
+    tab, p = [], _CRC_ONE >> 8  # x^8: one byte
+    for _ in range(64):
+        tab.append(p)
+        p = _crc_mulmod(p, p)
+    return tab
+
+
+_CRC_XPOW = _crc_xpow_table()  # x^(8 * 2^k)
+
+
+def crc32_shift(crc: int, nbytes: int) -> int:
+    """crc * x^(8*nbytes): what crc(A) contributes to the CRC of a string
+    in which nbytes more bytes follow A (nbytes < 2**64)."""
+    if not 0 <= nbytes < 1 << 64:
+        raise ValueError("nbytes out of range")
+    p, k = _CRC_ONE, 0
+    while nbytes:
+        if nbytes & 1:
+            p = _crc_mulmod(_CRC_XPOW[k], p)
+        nbytes >>= 1
+        k += 1
+    return _crc_mulmod(p, crc & 0xFFFFFFFF)
+
+
+def crc32_combine(c1: int, c2: int, len2: int) -> int:
+    """crc(A || B) from c1 = crc(A), c2 = crc(B), len2 = len(B)."""
+    return crc32_shift(c1, len2) ^ (c2 & 0xFFFFFFFF)
+
+
+def crc32_messages_reference(data: bytes | np.ndarray, msg_bytes: int,
+                             offs=None) -> np.ndarray:
+    """zlib.crc32 of each msg_bytes message, as uint32 array: message m
+    is data[offs[m] : offs[m] + msg_bytes], back to back without offs."""
+    buf = np.asarray(data, dtype=np.uint8).tobytes()
+    if offs is None:
+        assert len(buf) % msg_bytes == 0
+        offs = range(0, len(buf), msg_bytes)
+    out = []
+    for o in offs:
+        o = int(o)
+        assert 0 <= o and o + msg_bytes <= len(buf)
+        out.append(zlib.crc32(buf[o : o + msg_bytes]))
+    return np.array(out, dtype=np.uint32)
