@@ -6,15 +6,29 @@
 // impossible (CPU references for tests live in rocnrdma_amd/utils).
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <c10/cuda/CUDAGuard.h>
 
 #include "p2p_kernels.h"
 
 namespace {
 
-void check_buf(const torch::Tensor& t, const char* who) {
+const torch::Tensor& check_buf(const torch::Tensor& t, const char* who) {
   TORCH_CHECK(t.is_cuda(), who, ": tensor must be on GPU");
   TORCH_CHECK(t.is_contiguous(), who, ": tensor must be contiguous");
+  return t;
 }
+
+// How every binding starts: check the tensor it works on, make that
+// tensor's device current until the binding returns (allocations and
+// the launch follow the tensor, not whatever device the caller left
+// current), and pick up that device's current stream.
+struct OnDeviceOf {
+  c10::cuda::CUDAGuard guard;
+  hipStream_t stream;
+  OnDeviceOf(const torch::Tensor& t, const char* who)
+      : guard(check_buf(t, who).device()),
+        stream(at::cuda::getCurrentCUDAStream().stream()) {}
+};
 
 uint64_t nbytes_of(const torch::Tensor& t) {
   return (uint64_t)t.numel() * t.element_size();
@@ -28,33 +42,30 @@ uint64_t nbytes_of(const torch::Tensor& t) {
   } while (0)
 
 void fill_(torch::Tensor buf, int64_t seed) {
-  check_buf(buf, "fill_");
-  auto stream = at::cuda::getCurrentCUDAStream();
+  OnDeviceOf dev(buf, "fill_");
   HIP_OK(rocp2p_fill(buf.data_ptr(), nbytes_of(buf), (uint64_t)seed,
-                     stream.stream()));
+                     dev.stream));
 }
 
 int64_t verify(torch::Tensor buf, int64_t seed) {
-  check_buf(buf, "verify");
+  OnDeviceOf dev(buf, "verify");
   auto mis = torch::zeros({1}, torch::dtype(torch::kInt64).device(buf.device()));
-  auto stream = at::cuda::getCurrentCUDAStream();
   HIP_OK(rocp2p_verify(buf.data_ptr(), nbytes_of(buf), (uint64_t)seed,
                        (unsigned long long*)mis.data_ptr<int64_t>(),
-                       stream.stream()));
+                       dev.stream));
   return mis.item<int64_t>();
 }
 
 torch::Tensor crc32_pages(torch::Tensor buf) {
-  check_buf(buf, "crc32_pages");
+  OnDeviceOf dev(buf, "crc32_pages");
   uint64_t nbytes = nbytes_of(buf);
   TORCH_CHECK(nbytes % 4096 == 0, "crc32_pages: length must be 4 KiB pages");
   int64_t npages = (int64_t)(nbytes / 4096);
   auto out =
       torch::empty({npages}, torch::dtype(torch::kInt32).device(buf.device()));
-  auto stream = at::cuda::getCurrentCUDAStream();
   HIP_OK(rocp2p_crc32_pages(buf.data_ptr(), (uint64_t)npages,
                             (uint32_t*)out.data_ptr<int32_t>(),
-                            stream.stream()));
+                            dev.stream));
   return out;
 }
 
@@ -69,19 +80,10 @@ void check_align16(const torch::Tensor& t, const char* who) {
               ": base address must be 16-byte aligned");
 }
 
-// Caller-owned scratch for the digest launchers, from the caching
-// allocator on the current stream (0 bytes for the fused kernel).
-torch::Tensor digest_scratch(const torch::Tensor& like, uint64_t msg_bytes,
-                             uint32_t n) {
-  uint64_t bytes = rocp2p_crc32_msgs_scratch_bytes(msg_bytes, n);
-  return torch::empty({(int64_t)bytes},
-                      torch::dtype(torch::kUInt8).device(like.device()));
-}
-
 torch::Tensor crc32_messages(torch::Tensor region, int64_t msg_bytes,
                              c10::optional<torch::Tensor> offs,
                              int64_t grid_cap) {
-  check_buf(region, "crc32_messages");
+  OnDeviceOf dev(region, "crc32_messages");
   check_align16(region, "crc32_messages");
   TORCH_CHECK(msg_bytes > 0 && msg_bytes % 16 == 0,
               "crc32_messages: msg_bytes must be a non-zero multiple of 16");
@@ -106,76 +108,66 @@ torch::Tensor crc32_messages(torch::Tensor region, int64_t msg_bytes,
   auto out =
       torch::empty({n}, torch::dtype(torch::kInt32).device(region.device()));
   if (!n) return out;
-  auto scratch = digest_scratch(region, (uint64_t)msg_bytes, (uint32_t)n);
-  auto stream = at::cuda::getCurrentCUDAStream();
   HIP_OK(rocp2p_crc32_msgs(region.data_ptr(), d_offs, (uint64_t)msg_bytes,
                            (uint32_t)n, (uint32_t*)out.data_ptr<int32_t>(),
-                           scratch.data_ptr(), (uint32_t)grid_cap,
-                           stream.stream()));
+                           (uint32_t)grid_cap, dev.stream));
   return out;
 }
 
 int64_t crc32(torch::Tensor buf, int64_t grid_cap) {
-  check_buf(buf, "crc32");
+  OnDeviceOf dev(buf, "crc32");
   check_align16(buf, "crc32");
   TORCH_CHECK(grid_cap >= 0 && grid_cap <= 0xffffffffLL,
               "crc32: grid_cap out of range");
   uint64_t nbytes = nbytes_of(buf);
   auto out =
       torch::empty({1}, torch::dtype(torch::kInt32).device(buf.device()));
-  auto scratch = digest_scratch(buf, nbytes, 1);
-  auto stream = at::cuda::getCurrentCUDAStream();
   HIP_OK(rocp2p_crc32_region(buf.data_ptr(), nbytes,
                              (uint32_t*)out.data_ptr<int32_t>(),
-                             scratch.data_ptr(), (uint32_t)grid_cap,
-                             stream.stream()));
+                             (uint32_t)grid_cap, dev.stream));
   return (int64_t)(uint32_t)out.item<int32_t>();
 }
 
 void gather_(torch::Tensor region, torch::Tensor dst_offs,
              torch::Tensor src_addrs, int64_t msg_bytes) {
-  check_buf(region, "gather_");
+  OnDeviceOf dev(region, "gather_");
   check_u64_dev(dst_offs, "gather_");
   check_u64_dev(src_addrs, "gather_");
   TORCH_CHECK(dst_offs.numel() == src_addrs.numel(), "gather_: n mismatch");
-  auto stream = at::cuda::getCurrentCUDAStream();
   HIP_OK(rocp2p_gather(region.data_ptr(),
                        (const uint64_t*)dst_offs.data_ptr<int64_t>(),
                        (const uint64_t*)src_addrs.data_ptr<int64_t>(),
                        (uint64_t)msg_bytes, (uint32_t)dst_offs.numel(),
-                       stream.stream()));
+                       dev.stream));
 }
 
 void scatter_(torch::Tensor region, torch::Tensor src_offs,
               torch::Tensor dst_addrs, int64_t msg_bytes) {
-  check_buf(region, "scatter_");
+  OnDeviceOf dev(region, "scatter_");
   check_u64_dev(src_offs, "scatter_");
   check_u64_dev(dst_addrs, "scatter_");
   TORCH_CHECK(src_offs.numel() == dst_addrs.numel(), "scatter_: n mismatch");
-  auto stream = at::cuda::getCurrentCUDAStream();
   HIP_OK(rocp2p_scatter(region.data_ptr(),
                         (const uint64_t*)src_offs.data_ptr<int64_t>(),
                         (const uint64_t*)dst_addrs.data_ptr<int64_t>(),
                         (uint64_t)msg_bytes, (uint32_t)src_offs.numel(),
-                        stream.stream()));
+                        dev.stream));
 }
 
 void copy_(torch::Tensor dst, torch::Tensor src) {
-  check_buf(dst, "copy_");
+  OnDeviceOf dev(dst, "copy_");
   check_buf(src, "copy_");
   TORCH_CHECK(nbytes_of(dst) == nbytes_of(src), "copy_: size mismatch");
-  auto stream = at::cuda::getCurrentCUDAStream();
   HIP_OK(rocp2p_copy(dst.data_ptr(), src.data_ptr(), nbytes_of(dst),
-                     stream.stream()));
+                     dev.stream));
 }
 
 void copy_nt_(torch::Tensor dst, torch::Tensor src) {
-  check_buf(dst, "copy_nt_");
+  OnDeviceOf dev(dst, "copy_nt_");
   check_buf(src, "copy_nt_");
   TORCH_CHECK(nbytes_of(dst) == nbytes_of(src), "copy_nt_: size mismatch");
-  auto stream = at::cuda::getCurrentCUDAStream();
   HIP_OK(rocp2p_copy_nt(dst.data_ptr(), src.data_ptr(), nbytes_of(dst),
-                        stream.stream()));
+                        dev.stream));
 }
 
 // Export an HBM range as a dmabuf fd — the GPU half of the verbs
@@ -183,7 +175,7 @@ void copy_nt_(torch::Tensor dst, torch::Tensor src) {
 // GPU-only box validate that machinery without an HCA.  Caller owns
 // the fd (os.close it).
 int64_t dmabuf_fd(torch::Tensor buf) {
-  check_buf(buf, "dmabuf_fd");
+  OnDeviceOf dev(buf, "dmabuf_fd");
   int fd = -1;
   hipError_t e = hipMemGetHandleForAddressRange(
       &fd, buf.data_ptr(), nbytes_of(buf), hipMemRangeHandleTypeDmaBufFd,

@@ -6,9 +6,10 @@
 
 extern "C" {
 
-// One-time: upload CRC32 slice-by-8 tables, GF(2) shift matrices and the
-// byte-sliced x^(8n) power table to device constant memory.  Idempotent, cheap.
-hipError_t rocp2p_crc32_init();
+// No call here needs set-up.  The CRC entry points upload their lookup
+// tables (a compile-time constant, p2p_crc.h) to the current device
+// before that device's first CRC launch, under a lock: call them, like
+// every launch, with the device of `stream` current.
 
 // buf[i] = splitmix64(seed + (i+1)*GOLDEN) for each 8-byte word.
 // nbytes % 8 == 0.  HBM-streaming (16 B/lane vector stores).
@@ -38,21 +39,18 @@ hipError_t rocp2p_crc32_pages(const void* buf, uint64_t npages,
 // offset 16-byte aligned (host-visible violations: hipErrorInvalidValue).
 // region: one digest of any byte length (0 -> 0); buf 16-byte aligned;
 // never loads a byte at or beyond buf + nbytes.
-// d_scratch: rocp2p_crc32_msgs_scratch_bytes() bytes (region: query with
-// (nbytes, 1)); the fused kernel needs none, the query returns 0 and
-// null is accepted.
+// Chunk CRCs never leave the wave that computes them, so neither call
+// needs working memory.
 // grid_cap: 0 = tuned default; otherwise the maximum number of
 // workgroups (16 waves each).  A tuning and testing knob: it makes each
 // wave walk a multi-chunk run at test-sized inputs (the default grid
 // only does so above 16 MiB).
 hipError_t rocp2p_crc32_msgs(const void* base, const uint64_t* d_offs,
                              uint64_t msg_bytes, uint32_t n, uint32_t* d_out,
-                             void* d_scratch, uint32_t grid_cap,
-                             hipStream_t stream);
-uint64_t rocp2p_crc32_msgs_scratch_bytes(uint64_t msg_bytes, uint32_t n);
+                             uint32_t grid_cap, hipStream_t stream);
 hipError_t rocp2p_crc32_region(const void* buf, uint64_t nbytes,
-                               uint32_t* d_out, void* d_scratch,
-                               uint32_t grid_cap, hipStream_t stream);
+                               uint32_t* d_out, uint32_t grid_cap,
+                               hipStream_t stream);
 
 // Streaming device copy (bandwidth ceiling probe), 16 B/lane.
 hipError_t rocp2p_copy(void* dst, const void* src, uint64_t nbytes,

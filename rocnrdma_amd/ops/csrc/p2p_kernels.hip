@@ -5,20 +5,19 @@
 // integrity, and a streaming-copy bandwidth probe.  These are the "HIP
 // fill/CRC kernel (LDS-staged)" the north star requires: payloads are
 // generated AND verified in HBM, so zero-copy RDMA can be proven without
-// any host readback (the reference had no integrity path at all beyond a
-// broken single-sg mmap readback — reference: /root/reference/tests/
-// amdp2ptest.c:336-395).
+// any host readback.
 //
-// MI355X design notes (per /opt/skills/guides/MI355X_MICROARCH.md):
+// MI355X design notes:
 //  - wave64; all wave-width constants hard-coded 64;
 //  - streaming kernels move 16 B/lane/instruction (dwordx4), grid-stride
 //    with >> 256 workgroups to fill 8 XCDs;
 //  - CRC32: one wave per 4 KiB page, lane l owns bytes [64l, 64l+64);
 //    slice-by-8 tables (8 x 256 u32) live in LDS (random-access lookups,
-//    exactly what LDS is for); each lane's segment CRC is shifted by its
-//    tail length with 6 GF(2) 32x32 matrices (M(64B<<k)) also in LDS,
-//    then XOR-reduced across the wave with __shfl_xor (combine identity
-//    validated against zlib in tests/test_crc.py);
+//    exactly what LDS is for); the lanes' segment CRCs are merged by a
+//    6-level log tree of byte-sliced GF(2) shift operators (64 B << k),
+//    also in LDS.  The algebra and the tables are p2p_crc.h's, checked
+//    against zlib in tests/test_crc_digest.py (host) and
+//    tests/test_gpu_kernels.py, tests/test_gpu_crc_digest.py (device);
 //  - compute ceiling: ~8 table lookups per 8 B per lane; far above the
 //    PCIe/NIC rates this harness verifies, far below HBM peak by design
 //    (integrity pass, not the timed datapath).
@@ -26,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
+#include <mutex>
 #include "p2p_kernels.h"
 #include "p2p_crc.h"
 #include "p2p_pattern.h"
@@ -161,100 +161,96 @@ __global__ void k_copy_t(uint4_cv* __restrict__ dst,
 // small-message lines of the ib_write_bw sweep are PCIe-bound, not
 // launch-bound.  msg_bytes is uniform per batch (transport invariant).
 
+// Message m lives at region + offs[m] on one side and at the absolute
+// address addrs[m] on the other; GATHER copies addrs -> region, scatter
+// the other way.
 // vshift: log2(vecs_per_msg) when it is a power of two (uniform branch
 // avoids a 64-bit divide per 16-byte vector), else 0xffffffff.
-__global__ void k_gather(uint8_t* __restrict__ dst_base,
-                         const uint64_t* __restrict__ dst_offs,
-                         const uint64_t* __restrict__ src_addrs,
-                         uint64_t vecs_per_msg, uint64_t total_vecs,
-                         uint32_t vshift) {
+template <bool GATHER>
+__global__ void k_msg_engine(uint8_t* __restrict__ region,
+                             const uint64_t* __restrict__ offs,
+                             const uint64_t* __restrict__ addrs,
+                             uint64_t vecs_per_msg, uint64_t total_vecs,
+                             uint32_t vshift) {
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
        v < total_vecs; v += stride) {
     uint64_t msg = (vshift != 0xffffffffu) ? (v >> vshift)
                                            : (v / vecs_per_msg);
     uint64_t idx = v - msg * vecs_per_msg;
-    const uint4* src = reinterpret_cast<const uint4*>(src_addrs[msg]);
-    uint4* dst = reinterpret_cast<uint4*>(dst_base + dst_offs[msg]);
-    dst[idx] = src[idx];
-  }
-}
-
-__global__ void k_scatter(const uint8_t* __restrict__ src_base,
-                          const uint64_t* __restrict__ src_offs,
-                          const uint64_t* __restrict__ dst_addrs,
-                          uint64_t vecs_per_msg, uint64_t total_vecs,
-                          uint32_t vshift) {
-  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-       v < total_vecs; v += stride) {
-    uint64_t msg = (vshift != 0xffffffffu) ? (v >> vshift)
-                                           : (v / vecs_per_msg);
-    uint64_t idx = v - msg * vecs_per_msg;
-    const uint4* src =
-        reinterpret_cast<const uint4*>(src_base + src_offs[msg]);
-    uint4* dst = reinterpret_cast<uint4*>(dst_addrs[msg]);
-    dst[idx] = src[idx];
+    uint4* inside = reinterpret_cast<uint4*>(region + offs[msg]);
+    uint4* outside = reinterpret_cast<uint4*>(addrs[msg]);
+    if (GATHER)
+      inside[idx] = outside[idx];
+    else
+      outside[idx] = inside[idx];
   }
 }
 
 // ---------------------------------------------------------------------
 // CRC32 (zlib polynomial 0xEDB88320, init/xorout 0xFFFFFFFF)
 
-__constant__ uint32_t c_crc_tab[8][256];   // slice-by-8
-// Byte-sliced GF(2) shift operators: c_shift_tab[k][b][v] = M(64B<<k)
-// applied to (v << 8b).  Applying a 32x32 GF(2) matrix becomes 4 table
-// lookups instead of 32 serial dependent steps.
-__constant__ uint32_t c_shift_tab[6][4][256];
+// slice: slicing-by-8.  shift[k]: byte-sliced GF(2) operator "64 B << k
+// follow" (applying a 32x32 GF(2) matrix becomes 4 lookups instead of
+// 32 serial dependent steps).  xpow8: x^(8 * v * 256^j) mod P.
+// Uploaded by crc_tables_ready(), once per device: holding the same
+// bytes as constant-initialised data of the code object instead cost
+// k_crc32_pages, which stages them 8192 times per GiB, 7-9%
+// (docs/PERF.md §2).
+__constant__ rocp2p_crc_tables c_crc;
 
-static bool g_crc_ready = false;
+// The 32 KiB a CRC workgroup keeps in LDS.
+struct crc_lds {
+  uint32_t slice[8][256];
+  uint32_t shift[6][4][256];
+};
 
-static void host_make_tables(uint32_t tab[8][256],
-                             uint32_t stab[6][4][256]) {
-  const uint32_t POLY = 0xEDB88320u;
-  for (uint32_t i = 0; i < 256; i++) {
-    uint32_t c = i;
-    for (int k = 0; k < 8; k++) c = (c & 1) ? (c >> 1) ^ POLY : c >> 1;
-    tab[0][i] = c;
-  }
-  for (int t = 1; t < 8; t++)
-    for (uint32_t i = 0; i < 256; i++)
-      tab[t][i] = (tab[t - 1][i] >> 8) ^ tab[0][tab[t - 1][i] & 0xff];
+// Stage the slice-by-8 table and the shift operators; ends with the
+// barrier that makes them visible to the workgroup.
+__device__ __forceinline__ void crc_stage_tables(crc_lds& s) {
+  for (uint32_t i = threadIdx.x; i < 8 * 256; i += blockDim.x)
+    (&s.slice[0][0])[i] = (&c_crc.slice[0][0])[i];
+  for (uint32_t i = threadIdx.x; i < 6 * 4 * 256; i += blockDim.x)
+    (&s.shift[0][0][0])[i] = (&c_crc.shift[0][0][0])[i];
+  __syncthreads();
+}
 
-  // GF(2) matrices: odd = shift-by-1-bit operator, square to double.
-  uint32_t m1[32], m2[32];
-  m1[0] = POLY;
-  for (int i = 1; i < 32; i++) m1[i] = 1u << (i - 1);
-  auto times = [](const uint32_t* m, uint32_t v) {
-    uint32_t s = 0;
-    for (int i = 0; v; v >>= 1, i++)
-      if (v & 1) s ^= m[i];
-    return s;
-  };
-  auto square = [&](const uint32_t* in, uint32_t* out) {
-    for (int i = 0; i < 32; i++) out[i] = times(in, in[i]);
-  };
-  // m1: 1 bit -> square 3x => 8 bits (1 byte)
-  square(m1, m2);        // 2 bits
-  square(m2, m1);        // 4 bits
-  square(m1, m2);        // 8 bits = 1 byte (in m2)
-  // 1B -> 64B: square 6 more times
-  uint32_t cur[32];
-  for (int i = 0; i < 32; i++) cur[i] = m2[i];
+// zlib crc32 of a 4 KiB chunk, returned in every lane of the wave that
+// calls it; seg = this lane's 64-byte segment (4x dwordx4 loads).
+__device__ __forceinline__ uint32_t crc_page(const uint8_t* seg, uint32_t lane,
+                                             const crc_lds& s) {
+  uint4 v0 = reinterpret_cast<const uint4*>(seg)[0];
+  uint4 v1 = reinterpret_cast<const uint4*>(seg)[1];
+  uint4 v2 = reinterpret_cast<const uint4*>(seg)[2];
+  uint4 v3 = reinterpret_cast<const uint4*>(seg)[3];
+  uint32_t w[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w,
+                    v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
+  uint32_t crc = 0xFFFFFFFFu;
+#pragma unroll
+  for (int i = 0; i < 8; i++)
+    crc = rocp2p_crc_step8(s.slice, crc, w[2 * i], w[2 * i + 1]);
+  crc ^= 0xFFFFFFFFu;
+
+  // Log-tree combine: level k merges adjacent spans of 64B<<k.
+  // combine(cL, cR) = shift(cL, span) ^ cR; shift is linear over XOR, so
+  // the tree equals the flat XOR-of-shifted-lane-CRCs identity.  The
+  // shift operator is UNIFORM per level, and the tree doubles as the
+  // wave reduction — every lane ends holding the page CRC.
+#pragma unroll
   for (int k = 0; k < 6; k++) {
-    square(cur, m1);
-    for (int i = 0; i < 32; i++) cur[i] = m1[i];
-  }  // cur = shift by 64 bytes
-  for (int k = 0; k < 6; k++) {
-    for (int b = 0; b < 4; b++)
-      for (uint32_t v = 0; v < 256; v++)
-        stab[k][b][v] = times(cur, v << (8 * b));
-    square(cur, m1);
-    for (int i = 0; i < 32; i++) cur[i] = m1[i];
+    uint32_t partner = __shfl_xor(crc, 1u << k, WAVE);
+    bool left = ((lane >> k) & 1u) == 0;
+    uint32_t cl = left ? crc : partner;
+    uint32_t cr = left ? partner : crc;
+    crc = rocp2p_crc_apply(s.shift[k], cl) ^ cr;
   }
+  return crc;
 }
 
 // One wave per 4 KiB page; 4 waves (256 threads) per workgroup.
+// Not yet built on crc_stage_tables / crc_page: that form has only
+// been measured together with another change that cost this kernel
+// 5-8% at 1 GiB (docs/PERF.md §2).
 __global__ void __launch_bounds__(256) k_crc32_pages(
     const uint32_t* __restrict__ buf, uint64_t npages,
     uint32_t* __restrict__ out) {
@@ -263,9 +259,9 @@ __global__ void __launch_bounds__(256) k_crc32_pages(
 
   // stage tables into LDS (8 KB slice-by-8 + 24 KB shift operators)
   for (uint32_t i = threadIdx.x; i < 8 * 256; i += blockDim.x)
-    (&s_tab[0][0])[i] = (&c_crc_tab[0][0])[i];
+    (&s_tab[0][0])[i] = (&c_crc.slice[0][0])[i];
   for (uint32_t i = threadIdx.x; i < 6 * 4 * 256; i += blockDim.x)
-    (&s_stab[0][0][0])[i] = (&c_shift_tab[0][0][0])[i];
+    (&s_stab[0][0][0])[i] = (&c_crc.shift[0][0][0])[i];
   __syncthreads();
 
   const uint32_t lane = threadIdx.x & (WAVE - 1);
@@ -297,13 +293,7 @@ __global__ void __launch_bounds__(256) k_crc32_pages(
     }
     crc ^= 0xFFFFFFFFu;
 
-    // Log-tree combine: level k merges adjacent spans of 64B<<k.
-    // combine(cL, cR) = shift(cL, span) ^ cR; shift is linear over
-    // XOR, so the tree equals the flat XOR-of-shifted-lane-CRCs
-    // identity validated against zlib in tests/test_pattern.py.  The
-    // shift matrix is UNIFORM per level (byte-sliced: 4 LDS lookups),
-    // and the tree doubles as the wave reduction — every lane ends
-    // holding the page CRC.
+    // uniform log tree, as in crc_page
 #pragma unroll
     for (int k = 0; k < 6; k++) {
       uint32_t partner = __shfl_xor(crc, 1u << k, WAVE);
@@ -323,8 +313,8 @@ __global__ void __launch_bounds__(256) k_crc32_pages(
 // Every message is cut into 4 KiB chunks from its own start plus at
 // most one partial chunk; chunks are numbered message-major and each
 // WAVE owns a contiguous run of them (run length chosen by the
-// launcher).  Full chunks reuse the page scheme above (slice-by-8 +
-// uniform log tree, same LDS tables, same 32 KB per workgroup).
+// launcher).  Full chunks go through crc_page (same LDS tables, same
+// 32 KB per workgroup).
 // Inside a run the wave carries acc = crc(chunks so far of this
 // message): acc = shift(acc, 4096) ^ crc(chunk), the 4 KiB shift being
 // the level-5 (2 KiB) operator applied twice — 8 LDS lookups, no extra
@@ -347,30 +337,10 @@ __global__ void __launch_bounds__(256) k_crc32_pages(
 // wave XOR-reduces.  No byte at or beyond the message end is loaded:
 // the last partial 16 bytes are fetched with 8/4/2/1-byte loads.
 
-__constant__ uint32_t c_xpow8[8][256];  // x^(8 * v * 256^j) mod P
-
-typedef uint32_t crc_tab256[256];
-
-__device__ __forceinline__ uint32_t crc_step8(const crc_tab256* t,
-                                              uint32_t crc, uint32_t lo,
-                                              uint32_t hi) {
-  uint32_t a = lo ^ crc;
-  return t[7][a & 0xff] ^ t[6][(a >> 8) & 0xff] ^ t[5][(a >> 16) & 0xff] ^
-         t[4][a >> 24] ^ t[3][hi & 0xff] ^ t[2][(hi >> 8) & 0xff] ^
-         t[1][(hi >> 16) & 0xff] ^ t[0][hi >> 24];
-}
-
-// byte-sliced GF(2) operator applied to c (4 lookups)
-__device__ __forceinline__ uint32_t crc_apply(const crc_tab256* m,
-                                              uint32_t c) {
-  return m[0][c & 0xff] ^ m[1][(c >> 8) & 0xff] ^ m[2][(c >> 16) & 0xff] ^
-         m[3][c >> 24];
-}
-
 // x^(8*r) in lane 0 (r uniform; other lanes hold partial products).
 __device__ __forceinline__ uint32_t crc_xpow_wave(uint64_t r, uint32_t lane) {
   const uint32_t j = lane & 7;  // lanes 8.. mirror 0..7
-  uint32_t t = c_xpow8[j][(r >> (8 * j)) & 0xff];
+  uint32_t t = c_crc.xpow8[j][(r >> (8 * j)) & 0xff];
   // level k folds bytes 2^k apart: needed once r has a byte 2^k or above
 #pragma unroll
   for (int k = 0; k < 3; k++)
@@ -413,14 +383,14 @@ __device__ __forceinline__ void crc_load_partial(const uint8_t* seg,
 }
 
 // zlib crc32 of the first nb (0..64) bytes held in w[16]
-__device__ __forceinline__ uint32_t crc_bytes64(const crc_tab256* t,
+__device__ __forceinline__ uint32_t crc_bytes64(const rocp2p_crc_tab256* t,
                                                 const uint32_t w[16],
                                                 uint32_t nb) {
   uint32_t crc = 0xFFFFFFFFu;
   const uint32_t n8 = nb >> 3, rem = nb & 7;
 #pragma unroll
   for (uint32_t i = 0; i < 8; i++)
-    if (i < n8) crc = crc_step8(t, crc, w[2 * i], w[2 * i + 1]);
+    if (i < n8) crc = rocp2p_crc_step8(t, crc, w[2 * i], w[2 * i + 1]);
   if (rem) {
     uint32_t lo = 0, hi = 0;
 #pragma unroll
@@ -442,14 +412,8 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
     const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
     uint64_t msg_bytes, uint64_t cpm, uint64_t total, uint64_t run,
     uint32_t* __restrict__ out) {
-  __shared__ uint32_t s_tab[8][256];
-  __shared__ uint32_t s_stab[6][4][256];
-
-  for (uint32_t i = threadIdx.x; i < 8 * 256; i += blockDim.x)
-    (&s_tab[0][0])[i] = (&c_crc_tab[0][0])[i];
-  for (uint32_t i = threadIdx.x; i < 6 * 4 * 256; i += blockDim.x)
-    (&s_stab[0][0][0])[i] = (&c_shift_tab[0][0][0])[i];
-  __syncthreads();
+  __shared__ crc_lds s;
+  crc_stage_tables(s);
 
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint32_t wv = threadIdx.x / WAVE, nwv = blockDim.x / WAVE;
@@ -476,27 +440,8 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
     const uint8_t* seg = mp + pos + lane * SEG;
     uint64_t done;  // message bytes [.., done) are covered by acc
     if (left >= PAGE) {
-      uint4 v0 = reinterpret_cast<const uint4*>(seg)[0];
-      uint4 v1 = reinterpret_cast<const uint4*>(seg)[1];
-      uint4 v2 = reinterpret_cast<const uint4*>(seg)[2];
-      uint4 v3 = reinterpret_cast<const uint4*>(seg)[3];
-      uint32_t w[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w,
-                        v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
-      uint32_t crc = 0xFFFFFFFFu;
-#pragma unroll
-      for (int i = 0; i < 8; i++)
-        crc = crc_step8(s_tab, crc, w[2 * i], w[2 * i + 1]);
-      crc ^= 0xFFFFFFFFu;
-      // uniform log tree, as in k_crc32_pages
-#pragma unroll
-      for (int k = 0; k < 6; k++) {
-        uint32_t partner = __shfl_xor(crc, 1u << k, WAVE);
-        bool is_left = ((lane >> k) & 1u) == 0;
-        uint32_t cl = is_left ? crc : partner;
-        uint32_t cr = is_left ? partner : crc;
-        crc = crc_apply(s_stab[k], cl) ^ cr;
-      }
-      acc = crc_apply(s_stab[5], crc_apply(s_stab[5], acc)) ^ crc;
+      acc = rocp2p_crc_apply(s.shift[5], rocp2p_crc_apply(s.shift[5], acc)) ^
+            crc_page(seg, lane, s);
       done = pos + PAGE;
     } else {
       const uint32_t valid = (uint32_t)left;  // 1..4095
@@ -507,8 +452,8 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
       uint32_t x = 0;
       if (nb)
         x = rocp2p_crc_mulmod(
-            rocp2p_crc_xpow8(valid - (beg + nb), c_xpow8),
-            crc_bytes64(s_tab, w, nb));
+            rocp2p_crc_xpow8(valid - (beg + nb), c_crc.xpow8),
+            crc_bytes64(s.slice, w, nb));
       for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
       if (lane == 0) atomicXor(&out[m], x);
       done = pos;  // acc (if any) still has `valid` bytes after it
@@ -543,7 +488,7 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
   // serialize in L2).  The tables are dead after the barrier; their
   // first words carry the hand-off.
   __syncthreads();
-  uint32_t* s_pend = &s_tab[0][0];
+  uint32_t* s_pend = &s.slice[0][0];
   if (lane == 0) {
     s_pend[2 * wv] = pend_f;
     s_pend[2 * wv + 1] = pend_m;
@@ -596,24 +541,25 @@ extern "C" hipError_t rocp2p_verify(const void* buf, uint64_t nbytes,
   return hipGetLastError();
 }
 
-extern "C" hipError_t rocp2p_copy(void* dst, const void* src, uint64_t nbytes,
-                                  hipStream_t stream) {
+template <bool NT>
+static hipError_t copy_launch(void* dst, const void* src, uint64_t nbytes,
+                              hipStream_t stream) {
   if (nbytes % 16) return hipErrorInvalidValue;
   uint64_t nvec = nbytes / 16;
   uint32_t grid = stream_grid(nvec / 4, 256);
-  hipLaunchKernelGGL(k_copy_t<false>, dim3(grid), dim3(256), 0, stream,
+  hipLaunchKernelGGL(k_copy_t<NT>, dim3(grid), dim3(256), 0, stream,
                      (uint4_cv*)dst, (const uint4_cv*)src, nvec);
   return hipGetLastError();
 }
 
+extern "C" hipError_t rocp2p_copy(void* dst, const void* src, uint64_t nbytes,
+                                  hipStream_t stream) {
+  return copy_launch<false>(dst, src, nbytes, stream);
+}
+
 extern "C" hipError_t rocp2p_copy_nt(void* dst, const void* src,
                                      uint64_t nbytes, hipStream_t stream) {
-  if (nbytes % 16) return hipErrorInvalidValue;
-  uint64_t nvec = nbytes / 16;
-  uint32_t grid = stream_grid(nvec / 4, 256);
-  hipLaunchKernelGGL(k_copy_t<true>, dim3(grid), dim3(256), 0, stream,
-                     (uint4_cv*)dst, (const uint4_cv*)src, nvec);
-  return hipGetLastError();
+  return copy_launch<true>(dst, src, nbytes, stream);
 }
 
 // The gather/scatter engine is PCIe-bound, not CU-bound: measured on
@@ -632,9 +578,9 @@ static uint32_t gather_grid_cap() {
   return (uint32_t)cap;
 }
 
-extern "C" hipError_t rocp2p_gather(void* dst_base,
-                                    const uint64_t* d_dst_offs,
-                                    const uint64_t* d_src_addrs,
+template <bool GATHER>
+static hipError_t msg_engine_launch(void* region, const uint64_t* d_offs,
+                                    const uint64_t* d_addrs,
                                     uint64_t msg_bytes, uint32_t n,
                                     hipStream_t stream) {
   if (msg_bytes % 16 || !msg_bytes) return hipErrorInvalidValue;
@@ -646,10 +592,19 @@ extern "C" hipError_t rocp2p_gather(void* dst_base,
   uint32_t vshift = (vecs_per_msg & (vecs_per_msg - 1))
                         ? 0xffffffffu
                         : (uint32_t)__builtin_ctzll(vecs_per_msg);
-  hipLaunchKernelGGL(k_gather, dim3(grid), dim3(256), 0, stream,
-                     (uint8_t*)dst_base, d_dst_offs, d_src_addrs,
-                     vecs_per_msg, total, vshift);
+  hipLaunchKernelGGL(k_msg_engine<GATHER>, dim3(grid), dim3(256), 0, stream,
+                     (uint8_t*)region, d_offs, d_addrs, vecs_per_msg, total,
+                     vshift);
   return hipGetLastError();
+}
+
+extern "C" hipError_t rocp2p_gather(void* dst_base,
+                                    const uint64_t* d_dst_offs,
+                                    const uint64_t* d_src_addrs,
+                                    uint64_t msg_bytes, uint32_t n,
+                                    hipStream_t stream) {
+  return msg_engine_launch<true>(dst_base, d_dst_offs, d_src_addrs, msg_bytes,
+                                 n, stream);
 }
 
 extern "C" hipError_t rocp2p_scatter(const void* src_base,
@@ -657,43 +612,32 @@ extern "C" hipError_t rocp2p_scatter(const void* src_base,
                                      const uint64_t* d_dst_addrs,
                                      uint64_t msg_bytes, uint32_t n,
                                      hipStream_t stream) {
-  if (msg_bytes % 16 || !msg_bytes) return hipErrorInvalidValue;
-  if (!n) return hipSuccess;
-  uint64_t vecs_per_msg = msg_bytes / 16;
-  uint64_t total = vecs_per_msg * n;
-  uint32_t grid = stream_grid(total, 256);
-  if (grid > gather_grid_cap()) grid = gather_grid_cap();
-  uint32_t vshift = (vecs_per_msg & (vecs_per_msg - 1))
-                        ? 0xffffffffu
-                        : (uint32_t)__builtin_ctzll(vecs_per_msg);
-  hipLaunchKernelGGL(k_scatter, dim3(grid), dim3(256), 0, stream,
-                     (const uint8_t*)src_base, d_src_offs, d_dst_addrs,
-                     vecs_per_msg, total, vshift);
-  return hipGetLastError();
+  // the scatter instantiation only reads the region
+  return msg_engine_launch<false>(const_cast<void*>(src_base), d_src_offs,
+                                  d_dst_addrs, msg_bytes, n, stream);
 }
 
-extern "C" hipError_t rocp2p_crc32_init() {
-  if (g_crc_ready) return hipSuccess;
-  static uint32_t tab[8][256];
-  static uint32_t stab[6][4][256];
-  host_make_tables(tab, stab);
-  hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_crc_tab), tab, sizeof(tab));
+// The tables are a compile-time constant (p2p_crc.h); each device that
+// runs a CRC kernel gets its copy before its first launch.  The device
+// of `stream` must be current, as for the launch itself.
+static hipError_t crc_tables_ready() {
+  static constexpr rocp2p_crc_tables tables = rocp2p_crc_make_tables();
+  static std::mutex mu;
+  static bool ready[64];  // by device ordinal
+  int dev;
+  hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
-  e = hipMemcpyToSymbol(HIP_SYMBOL(c_shift_tab), stab, sizeof(stab));
-  if (e != hipSuccess) return e;
-  static uint32_t xtab[ROCP2P_CRC_XPOW_N];
-  rocp2p_crc_xpow_table(xtab);
-  static uint32_t xtab8[8][256];
-  rocp2p_crc_xpow8_table(xtab8, xtab);
-  e = hipMemcpyToSymbol(HIP_SYMBOL(c_xpow8), xtab8, sizeof(xtab8));
-  if (e != hipSuccess) return e;
-  g_crc_ready = true;
-  return hipSuccess;
+  if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+  std::lock_guard<std::mutex> lock(mu);
+  if (ready[dev]) return hipSuccess;
+  e = hipMemcpyToSymbol(HIP_SYMBOL(c_crc), &tables, sizeof(tables));
+  ready[dev] = e == hipSuccess;
+  return e;
 }
 
 extern "C" hipError_t rocp2p_crc32_pages(const void* buf, uint64_t npages,
                                          uint32_t* d_out, hipStream_t stream) {
-  hipError_t e = rocp2p_crc32_init();
+  hipError_t e = crc_tables_ready();
   if (e != hipSuccess) return e;
   if (!npages) return hipSuccess;
   uint64_t blocks = (npages + 3) / 4;
@@ -716,7 +660,7 @@ static hipError_t crc32_digest_launch(const void* base,
                                       uint64_t msg_bytes, uint32_t n,
                                       uint32_t* d_out, uint32_t grid_cap,
                                       hipStream_t stream) {
-  hipError_t e = rocp2p_crc32_init();
+  hipError_t e = crc_tables_ready();
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
@@ -737,21 +681,11 @@ static hipError_t crc32_digest_launch(const void* base,
   return hipGetLastError();
 }
 
-// Fused design: chunk CRCs never leave the wave, so no scratch.
-extern "C" uint64_t rocp2p_crc32_msgs_scratch_bytes(uint64_t msg_bytes,
-                                                    uint32_t n) {
-  (void)msg_bytes;
-  (void)n;
-  return 0;
-}
-
 extern "C" hipError_t rocp2p_crc32_msgs(const void* base,
                                         const uint64_t* d_offs,
                                         uint64_t msg_bytes, uint32_t n,
-                                        uint32_t* d_out, void* d_scratch,
-                                        uint32_t grid_cap,
+                                        uint32_t* d_out, uint32_t grid_cap,
                                         hipStream_t stream) {
-  (void)d_scratch;
   if (msg_bytes % 16 || !msg_bytes || (uintptr_t)base % 16)
     return hipErrorInvalidValue;
   if (!n) return hipSuccess;
@@ -760,10 +694,8 @@ extern "C" hipError_t rocp2p_crc32_msgs(const void* base,
 }
 
 extern "C" hipError_t rocp2p_crc32_region(const void* buf, uint64_t nbytes,
-                                          uint32_t* d_out, void* d_scratch,
-                                          uint32_t grid_cap,
+                                          uint32_t* d_out, uint32_t grid_cap,
                                           hipStream_t stream) {
-  (void)d_scratch;
   if ((uintptr_t)buf % 16) return hipErrorInvalidValue;
   return crc32_digest_launch(buf, nullptr, nbytes, 1, d_out, grid_cap,
                              stream);

@@ -165,6 +165,7 @@ def test_soak_crc_audit_on_fake():
 _HEADER_PROG = r"""
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include <zlib.h>
 #include "p2p_crc.h"
@@ -176,6 +177,14 @@ static uint64_t rnd() {
 }
 #define CHECK(c) do { if (!(c)) { std::printf("FAIL line %d: %s\n", \
     __LINE__, #c); return 1; } } while (0)
+
+// The kernels hold this as constant-initialised device data, so it has
+// to stay a constant expression: one entry of each table known from
+// zlib (crc_table[0][1], x^8, x2n_table[9] = x^512).
+static constexpr rocp2p_crc_tables T = rocp2p_crc_make_tables();
+static_assert(T.slice[0][1] == 0x77073096u, "slice-by-8 table");
+static_assert(T.xpow8[0][1] == 0x00800000u, "byte-sliced power table");
+static_assert(T.shift[0][3][0x80] == 0x88d14467u, "shift operators");
 
 int main() {
   uint32_t tab[ROCP2P_CRC_XPOW_N];
@@ -220,6 +229,28 @@ int main() {
           (uint32_t)crc32_combine(ca, cb, (z_off_t)(n - k)));
     CHECK(rocp2p_crc_combine(ca, 0, 0, tab) == ca);
   }
+  // the kernels' tables: the run-time builders agree with the constant
+  CHECK(std::memcmp(t8, T.xpow8, sizeof(t8)) == 0);
+  // slice-by-8 over a 64-byte block, the way a lane walks its segment
+  for (int i = 0; i < 200; i++) {
+    const unsigned char* p = buf.data() + rnd() % (buf.size() - 64);
+    uint32_t w[16];
+    std::memcpy(w, p, 64);
+    uint32_t crc = 0xFFFFFFFFu;
+    for (int j = 0; j < 8; j++)
+      crc = rocp2p_crc_step8(T.slice, crc, w[2 * j], w[2 * j + 1]);
+    CHECK((crc ^ 0xFFFFFFFFu) == (uint32_t)crc32(0, p, 64));
+  }
+  // shift[k] appends 64 << k bytes: one level of the kernels' log tree
+  for (int k = 0; k < 6; k++)
+    for (int i = 0; i < 50; i++) {
+      size_t nb = (size_t)64 << k, na = rnd() % 5000;
+      const unsigned char* a = buf.data() + rnd() % (buf.size() - na - nb);
+      uint32_t ca = (uint32_t)crc32(0, a, (uInt)na);
+      uint32_t cb = (uint32_t)crc32(0, a + na, (uInt)nb);
+      CHECK((rocp2p_crc_apply(T.shift[k], ca) ^ cb) ==
+            (uint32_t)crc32(0, a, (uInt)(na + nb)));
+    }
   std::printf("OK\n");
   return 0;
 }

@@ -36,6 +36,90 @@ def test_fill_matches_reference(dev, nbytes):
     assert (got == ref).all()
 
 
+# -- the wave-tile split shared by fill / verify / copy --------------------
+# fill works in tiles of 8 KiB per wave, verify and copy in tiles of
+# 4 KiB; what is left after the last whole tile goes one 16-byte vector
+# per thread, and fill/verify end with an odd 8-byte word.
+GUARD = 64
+
+
+@pytest.mark.parametrize("nbytes", [8, 16, 24, 8184, 8192, 8216])
+def test_fill_tails(dev, nbytes):
+    """No vector at all, the odd word alone, and one tile -/+ a tail."""
+    import rocnrdma_amd.ops as ops
+    from rocnrdma_amd.utils import pattern
+
+    buf = torch.full((nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8,
+                     device=dev)
+    ops.fill_(buf[GUARD:GUARD + nbytes], seed=77)
+    got = buf.cpu().numpy()
+    assert (got[GUARD:GUARD + nbytes] == pattern.fill_reference(nbytes, 77)).all()
+    assert (got[:GUARD] == 0xA5).all() and (got[GUARD + nbytes:] == 0xA5).all()
+
+
+def test_verify_tail_word(dev):
+    import rocnrdma_amd.ops as ops
+
+    buf = torch.empty(8216, dtype=torch.uint8, device=dev)
+    ops.fill_(buf, seed=78)
+    assert ops.verify(buf, seed=78) == 0
+    buf[8216 - 3] ^= 0x10  # one bit of the odd last word
+    assert ops.verify(buf, seed=78) == 1
+
+
+@pytest.fixture(scope="module")
+def noise(dev):
+    """256 MiB + 8 KiB of random bytes, shared and never written."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    return torch.randint(0, 256, ((256 << 20) + 8192,), dtype=torch.uint8,
+                         device=dev, generator=g)
+
+
+@pytest.mark.parametrize("op", ["copy_", "copy_nt_"])
+@pytest.mark.parametrize("nbytes", [16, 4080, 4096, 4112])
+def test_copy_tails(dev, noise, op, nbytes):
+    import rocnrdma_amd.ops as ops
+
+    src = noise[4096 + 48:4096 + 48 + nbytes]
+    buf = torch.full((nbytes + 2 * GUARD,), 0x5A, dtype=torch.uint8,
+                     device=dev)
+    getattr(ops, op)(buf[GUARD:GUARD + nbytes], src)
+    torch.cuda.synchronize()
+    assert torch.equal(buf[GUARD:GUARD + nbytes], src)
+    assert (buf[:GUARD] == 0x5A).all() and (buf[GUARD + nbytes:] == 0x5A).all()
+
+
+# Past 256 MiB the grid caps are reached and a wave takes a second tile:
+# the only size at which the tile stride loop iterates.
+STRIDE_FILL = (256 << 20) + 8216
+STRIDE_COPY = (256 << 20) + 4112
+
+
+def test_fill_verify_stride_loop(dev):
+    import rocnrdma_amd.ops as ops
+    from rocnrdma_amd.utils import pattern
+
+    buf = torch.empty(STRIDE_FILL, dtype=torch.uint8, device=dev)
+    ops.fill_(buf, seed=9)
+    ref = torch.from_numpy(pattern.fill_reference(STRIDE_FILL, 9)).to(dev)
+    assert torch.equal(buf, ref)
+    assert ops.verify(buf, seed=9) == 0
+    buf[STRIDE_FILL - 5000] ^= 0x04  # in the second tile of wave 0
+    assert ops.verify(buf, seed=9) == 1
+
+
+@pytest.mark.parametrize("op", ["copy_", "copy_nt_"])
+def test_copy_stride_loop(dev, noise, op):
+    import rocnrdma_amd.ops as ops
+
+    src = noise[:STRIDE_COPY]
+    dst = torch.zeros_like(src)
+    getattr(ops, op)(dst, src)
+    torch.cuda.synchronize()
+    assert torch.equal(dst, src)
+
+
 def test_verify_counts_corruption(dev):
     import rocnrdma_amd.ops as ops
 
@@ -114,12 +198,14 @@ def test_sdma_transport_4kb_messages(dev, direction):
     tp.close()
 
 
-def test_gather_kernel_matches_reference(dev):
+# 48 B = 3 vectors per message: not a power of two, so the kernel
+# divides instead of shifting
+@pytest.mark.parametrize("msg", [48, 8192])
+def test_gather_kernel_matches_reference(dev, msg):
     """Direct gather_ use: scattered host-pinned slots -> chosen HBM
     offsets, compared against a CPU-composed reference."""
     import rocnrdma_amd.ops as ops
 
-    msg = 8192
     n = 37
     staging = torch.randint(0, 256, (n * msg,), dtype=torch.uint8,
                             pin_memory=True)
@@ -135,6 +221,58 @@ def test_gather_kernel_matches_reference(dev):
     for i in range(n):
         off = int(perm[i]) * msg
         assert torch.equal(got[off:off + msg], staging[i * msg:(i + 1) * msg])
+
+
+@pytest.mark.parametrize("msg", [48, 8192])
+def test_scatter_kernel_matches_reference(dev, msg):
+    """Direct scatter_ use: chosen HBM offsets -> host-pinned slots."""
+    import rocnrdma_amd.ops as ops
+
+    n = 37
+    region = torch.randint(0, 256, (n * msg,), dtype=torch.uint8, device=dev)
+    staging = torch.zeros(n * msg, dtype=torch.uint8, pin_memory=True)
+    perm = torch.randperm(n)
+    src_offs = (perm * msg).to(dtype=torch.int64, device=dev)
+    dst_addrs = torch.tensor(
+        [staging.data_ptr() + i * msg for i in range(n)],
+        dtype=torch.int64, device=dev)
+    ops.scatter_(region, src_offs, dst_addrs, msg)
+    torch.cuda.synchronize()
+    want = region.cpu()
+    for i in range(n):
+        off = int(perm[i]) * msg
+        assert torch.equal(staging[i * msg:(i + 1) * msg], want[off:off + msg])
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_kernels_run_on_the_tensors_device():
+    """Tensors on cuda:1 while cuda:0 is current, after cuda:0 has already
+    run a CRC kernel: launch, tables and outputs follow the tensor."""
+    import zlib
+
+    import rocnrdma_amd.ops as ops
+    from rocnrdma_amd.utils import pattern
+
+    d0, d1 = torch.device("cuda", 0), torch.device("cuda", 1)
+    torch.cuda.set_device(d0)
+    first = torch.randint(0, 256, (4 * 4096,), dtype=torch.uint8, device=d0)
+    assert (ops.crc32_pages(first).cpu().numpy().view(np.uint32) ==
+            pattern.crc32_pages_reference(first.cpu().numpy())).all()
+
+    buf = torch.empty(1 << 20, dtype=torch.uint8, device=d1)
+    ops.fill_(buf, seed=21)
+    assert (buf.cpu().numpy() == pattern.fill_reference(1 << 20, 21)).all()
+    assert ops.verify(buf, seed=21) == 0
+
+    data = torch.randint(0, 256, (257 * 4096,), dtype=torch.uint8, device=d1)
+    host = data.cpu().numpy()
+    crcs = ops.crc32_pages(data)
+    assert crcs.device == d1
+    assert (crcs.cpu().numpy().view(np.uint32) ==
+            pattern.crc32_pages_reference(host)).all()
+    n = 17 * 4096 + 1000
+    assert ops.crc32(data[:n]) == zlib.crc32(host[:n].tobytes())
+    assert torch.cuda.current_device() == 0
 
 
 def test_smoke_entry():
