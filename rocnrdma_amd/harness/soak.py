@@ -18,10 +18,15 @@ SIZES = [4 << 10, 16 << 10, 64 << 10, 256 << 10, 1 << 20, 4 << 20]
 
 def run_soak(transport: str = "auto", secs: float = 10.0,
              region_bytes: int = 256 << 20, seed: int = 1234,
-             device=None, metrics=None, audit: str = "pattern") -> dict:
+             device=None, metrics=None, audit: str = "pattern",
+             icrc: bool = False) -> dict:
     """audit="pattern": splitmix64 pattern + integrity_check (default).
     audit="crc": a seeded random payload per cycle through digest_check
-    (per-message CRC32, content-independent)."""
+    (per-message CRC32, content-independent).
+    icrc=True: the burst phase runs on a patterned, stamped sender with
+    every message's CRC32 checked inline; a cycle with a bad message is
+    a failure, and the stats gain icrc_checked / icrc_bad."""
+    from rocnrdma_amd.harness.sweep import pattern_sender
     from rocnrdma_amd.transport import get_transport
 
     if audit not in ("pattern", "crc"):
@@ -35,20 +40,34 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
     t_end = time.monotonic() + secs
     stats = {"cycles": 0, "msgs": 0, "bytes": 0, "audits": 0,
              "failures": 0}
+    extra = {}
+    if icrc:
+        extra["icrc"] = True
+        stats.update(icrc_checked=0, icrc_bad=0)
     while time.monotonic() < t_end:
         msg = rng.choice(SIZES)
         direction = rng.choice(["write", "read"])
         region = max(region_bytes // msg, 1) * msg
         tp = get_transport(transport, msg_bytes=msg, region_bytes=region,
-                           direction=direction, device=device)
+                           direction=direction, device=device, **extra)
         try:
-            # a few random bursts (bandwidth phase, content irrelevant)
+            if icrc:
+                pattern_sender(tp, seed=rng.getrandbits(32))
+                tp.stamp()
+            # a few random bursts (bandwidth phase; content irrelevant
+            # unless stamped)
             posted = 0
             for _ in range(rng.randint(1, 4)):
                 burst = rng.randint(1, max(2, tp.inflight))
                 tp.post_many(posted, burst)
                 posted += burst
                 tp.flush()
+            if icrc:
+                st = tp.icrc_stats()
+                stats["icrc_checked"] += st["checked"]
+                stats["icrc_bad"] += st["bad"]
+                if st["bad"]:
+                    stats["failures"] += 1
             # audit: full-region transfer + receiver verify
             if audit == "crc":
                 import numpy as np
@@ -84,6 +103,9 @@ def main():
                     default="pattern",
                     help="pattern: splitmix64 + verify; crc: random "
                          "payload + per-message CRC32 digests")
+    ap.add_argument("--icrc", action="store_true",
+                    help="run the burst phase stamped, every message's "
+                         "CRC32 checked inline")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="expose Prometheus metrics on this port")
     args = ap.parse_args()
@@ -91,7 +113,8 @@ def main():
 
     metrics = TransferMetrics(port=args.metrics_port or None)
     stats = run_soak(args.transport, args.secs, args.region_bytes,
-                     args.seed, metrics=metrics, audit=args.audit)
+                     args.seed, metrics=metrics, audit=args.audit,
+                     icrc=args.icrc)
     print(stats)
     raise SystemExit(1 if stats["failures"] else 0)
 

@@ -3,6 +3,7 @@ matrix (BASELINE configs 3): 4 KB … 64 MB x {write, read}, one QP
 analog per GPU.
 
 CLI:  python -m rocnrdma_amd.harness.sweep [--transport auto] [--out f.json]
+                                           [--icrc]
 """
 from __future__ import annotations
 
@@ -50,6 +51,30 @@ def run_point(tp, target_secs: float = 1.0, min_msgs: int = 8) -> dict:
     }
 
 
+def pattern_sender(tp, seed: int = 1) -> None:
+    """Give the sending side known content (staging slots for write, the
+    region for read) — what an icrc transport stamps before a run."""
+    import numpy as np
+
+    from rocnrdma_amd.utils import pattern
+
+    if tp.direction == "write":
+        ref = pattern.fill_reference(tp.inflight * tp.msg_bytes, seed)
+        for k in range(tp.inflight):
+            # numpy view of the slot (pinned torch tensor or ndarray)
+            np.asarray(tp.staging[k])[:] = \
+                ref[k * tp.msg_bytes:(k + 1) * tp.msg_bytes]
+    elif isinstance(tp.region, np.ndarray):
+        tp.region[:] = pattern.fill_reference(tp.region_bytes, seed)
+    else:
+        import torch
+
+        from rocnrdma_amd import ops
+
+        ops.fill_(tp.region, seed)
+        torch.cuda.synchronize(tp.region.device)
+
+
 def run_lat_point(tp, iters: int = 1000) -> dict:
     """ib_write_lat analog: single-message completion latency."""
     import time as _t
@@ -79,22 +104,33 @@ def run_sweep(transport: str = "auto", region_bytes: int = 1 << 30,
               sizes=None, directions=("write", "read"),
               target_secs: float = 1.0, device=None,
               num_streams: int = 2, inflight: int | None = 0,
-              lat_iters: int = 0) -> list[dict]:
+              lat_iters: int = 0, icrc: bool = False) -> list[dict]:
+    """icrc=True: every point runs on an icrc transport whose sender was
+    patterned and stamped first, so each timed message is digested while
+    it moves and compared; rows gain icrc_checked / icrc_bad."""
     from rocnrdma_amd.transport import get_transport
 
     rows = []
+    extra = {"icrc": True} if icrc else {}
     for direction in directions:
         for msg in sizes or DEFAULT_SIZES:
             region = max(region_bytes // msg, 1) * msg
             tp = get_transport(transport, msg_bytes=msg,
                                region_bytes=region, direction=direction,
                                device=device, num_streams=num_streams,
-                               inflight=inflight)
+                               inflight=inflight, **extra)
             try:
+                if icrc:
+                    pattern_sender(tp)
+                    tp.stamp()
                 if lat_iters:
                     row = run_lat_point(tp, lat_iters)
                 else:
                     row = run_point(tp, target_secs=target_secs)
+                if icrc:
+                    st = tp.icrc_stats()
+                    row["icrc_checked"] = st["checked"]
+                    row["icrc_bad"] = st["bad"]
                 row["transport"] = tp.name
                 rows.append(row)
             finally:
@@ -113,6 +149,10 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--lat", type=int, default=0,
                     help="latency mode: N single-message iterations")
+    ap.add_argument("--icrc", action="store_true",
+                    help="stamp the sender and check every message's "
+                         "CRC32 inline while it moves (kernel engine: "
+                         "sizes below 8 MiB)")
     args = ap.parse_args()
 
     sizes = ([int(s) for s in args.sizes.split(",")] if args.sizes
@@ -123,7 +163,11 @@ def main():
         args.region_bytes = min(args.region_bytes, 256 << 20)
     rows = run_sweep(args.transport, args.region_bytes, sizes,
                      target_secs=args.secs, num_streams=args.streams,
-                     inflight=args.inflight, lat_iters=args.lat)
+                     inflight=args.inflight, lat_iters=args.lat,
+                     icrc=args.icrc)
+    if args.icrc:
+        print("icrc: checked", sum(r["icrc_checked"] for r in rows),
+              "bad", sum(r["icrc_bad"] for r in rows))
     if args.lat:
         print(f"{'msg':>12} {'dir':>6} {'us_min':>8} {'us_p50':>8} "
               f"{'us_p99':>8} {'us_max':>8}")

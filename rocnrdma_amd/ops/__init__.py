@@ -86,6 +86,27 @@ def scatter_(region: torch.Tensor, src_offs: torch.Tensor,
     _require().scatter_(region, src_offs, dst_addrs, msg_bytes)
 
 
+def gather_crc_(region: torch.Tensor, dst_offs: torch.Tensor,
+                src_addrs: torch.Tensor, msg_bytes: int, *,
+                grid_cap: int = 0) -> torch.Tensor:
+    """gather_ with an inline ICRC: the same launch moves the batch and
+    returns zlib's CRC32 of every message as it was loaded over the link
+    (int32 tensor[n] on the region's device, no sync; view as uint32).
+    grid_cap caps the workgroup count below the engine's own cap (0 =
+    default) — a tuning and testing knob."""
+    return _require().gather_crc_(region, dst_offs, src_addrs, msg_bytes,
+                                  grid_cap)
+
+
+def scatter_crc_(region: torch.Tensor, src_offs: torch.Tensor,
+                 dst_addrs: torch.Tensor, msg_bytes: int, *,
+                 grid_cap: int = 0) -> torch.Tensor:
+    """scatter_ with an inline ICRC: digests are of the HBM bytes as they
+    were loaded on their way to the host-pinned destinations."""
+    return _require().scatter_crc_(region, src_offs, dst_addrs, msg_bytes,
+                                   grid_cap)
+
+
 def dmabuf_fd(buf: torch.Tensor) -> int:
     """Export an HBM tensor as a dmabuf fd (ibv_reg_dmabuf_mr's GPU
     half). Caller must os.close() the fd."""

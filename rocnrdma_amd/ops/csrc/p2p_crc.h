@@ -123,9 +123,25 @@ struct rocp2p_crc_tables {
   uint32_t slice[8][256];     // slicing-by-8
   uint32_t shift[6][4][256];  // shift[k][b][v] = (v << 8b) * x^(8 * 64 * 2^k)
   uint32_t xpow8[8][256];     // rocp2p_crc_xpow8_table
+  // Added behind the three above so that none of their offsets moves:
+  // shift16[k][b][v] = (v << 8b) * x^(8 * 16 * 2^k), the 16- and 32-byte
+  // operators under shift[0] in the inline-ICRC engine's lane tree.
+  uint32_t shift16[2][4][256];
 };
 
-// All three, as one constant expression: 40 KiB that depend on nothing
+// One level of a byte-sliced shift operator: m[b][v] = (v << 8b) * p.
+constexpr void rocp2p_crc_shift_level(uint32_t m[4][256], uint32_t p) {
+  uint32_t bit[32] = {};  // (1 << i) * p; the rest by linearity
+  for (int i = 0; i < 32; i++) bit[i] = rocp2p_crc_mulmod(p, 1u << i);
+  for (int b = 0; b < 4; b++)
+    for (uint32_t v = 0; v < 256; v++) {
+      uint32_t s = 0;
+      for (int j = 0; j < 8; j++) s ^= (0u - ((v >> j) & 1u)) & bit[8 * b + j];
+      m[b][v] = s;
+    }
+}
+
+// All four, as one constant expression: 48 KiB that depend on nothing
 // at run time.
 constexpr rocp2p_crc_tables rocp2p_crc_make_tables() {
   rocp2p_crc_tables t = {};
@@ -142,17 +158,9 @@ constexpr rocp2p_crc_tables rocp2p_crc_make_tables() {
 
   uint32_t xp[ROCP2P_CRC_XPOW_N] = {};
   rocp2p_crc_xpow_table(xp);
-  for (int k = 0; k < 6; k++) {
-    uint32_t bit[32] = {};  // (1 << i) * x^(8 * 64 * 2^k); rest by linearity
-    for (int i = 0; i < 32; i++) bit[i] = rocp2p_crc_mulmod(xp[6 + k], 1u << i);
-    for (int b = 0; b < 4; b++)
-      for (uint32_t v = 0; v < 256; v++) {
-        uint32_t s = 0;
-        for (int j = 0; j < 8; j++) s ^= (0u - ((v >> j) & 1u)) & bit[8 * b + j];
-        t.shift[k][b][v] = s;
-      }
-  }
+  for (int k = 0; k < 6; k++) rocp2p_crc_shift_level(t.shift[k], xp[6 + k]);
   rocp2p_crc_xpow8_table(t.xpow8, xp);
+  for (int k = 0; k < 2; k++) rocp2p_crc_shift_level(t.shift16[k], xp[4 + k]);
   return t;
 }
 #endif  // C++14

@@ -154,6 +154,43 @@ void scatter_(torch::Tensor region, torch::Tensor src_offs,
                         dev.stream));
 }
 
+// gather_/scatter_ with the inline ICRC: same checks and prologue, plus
+// the digest tensor (int32[n] on the region's device, no sync).
+template <typename Launch>
+torch::Tensor msg_engine_crc(const char* who, Launch launch,
+                             torch::Tensor region, torch::Tensor offs,
+                             torch::Tensor addrs, int64_t msg_bytes,
+                             int64_t grid_cap) {
+  OnDeviceOf dev(region, who);
+  check_u64_dev(offs, who);
+  check_u64_dev(addrs, who);
+  TORCH_CHECK(offs.numel() == addrs.numel(), who, ": n mismatch");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= 0xffffffffLL, who,
+              ": grid_cap out of range");
+  auto out = torch::empty({offs.numel()},
+                          torch::dtype(torch::kInt32).device(region.device()));
+  HIP_OK(launch(region.data_ptr(), (const uint64_t*)offs.data_ptr<int64_t>(),
+                (const uint64_t*)addrs.data_ptr<int64_t>(),
+                (uint64_t)msg_bytes, (uint32_t)offs.numel(),
+                (uint32_t*)out.data_ptr<int32_t>(), (uint32_t)grid_cap,
+                dev.stream));
+  return out;
+}
+
+torch::Tensor gather_crc_(torch::Tensor region, torch::Tensor dst_offs,
+                          torch::Tensor src_addrs, int64_t msg_bytes,
+                          int64_t grid_cap) {
+  return msg_engine_crc("gather_crc_", rocp2p_gather_crc, region, dst_offs,
+                        src_addrs, msg_bytes, grid_cap);
+}
+
+torch::Tensor scatter_crc_(torch::Tensor region, torch::Tensor src_offs,
+                           torch::Tensor dst_addrs, int64_t msg_bytes,
+                           int64_t grid_cap) {
+  return msg_engine_crc("scatter_crc_", rocp2p_scatter_crc, region, src_offs,
+                        dst_addrs, msg_bytes, grid_cap);
+}
+
 void copy_(torch::Tensor dst, torch::Tensor src) {
   OnDeviceOf dev(dst, "copy_");
   check_buf(src, "copy_");
@@ -205,6 +242,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "batched message engine: host-pinned srcs -> HBM region offsets");
   m.def("scatter_", &scatter_,
         "batched message engine: HBM region offsets -> host-pinned dsts");
+  m.def("gather_crc_", &gather_crc_,
+        "gather_ plus one zlib CRC32 per message, taken in the same pass",
+        py::arg("region"), py::arg("dst_offs"), py::arg("src_addrs"),
+        py::arg("msg_bytes"), py::arg("grid_cap") = 0);
+  m.def("scatter_crc_", &scatter_crc_,
+        "scatter_ plus one zlib CRC32 per message, taken in the same pass",
+        py::arg("region"), py::arg("src_offs"), py::arg("dst_addrs"),
+        py::arg("msg_bytes"), py::arg("grid_cap") = 0);
   m.def("dmabuf_fd", &dmabuf_fd,
         "export an HBM tensor range as a dmabuf fd (caller closes)");
 }

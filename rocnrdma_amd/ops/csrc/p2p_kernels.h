@@ -71,4 +71,25 @@ hipError_t rocp2p_scatter(const void* src_base, const uint64_t* d_src_offs,
                           const uint64_t* d_dst_addrs, uint64_t msg_bytes,
                           uint32_t n, hipStream_t stream);
 
+// The same engine with an inline ICRC: one launch moves the batch and
+// leaves d_out[m] = zlib crc32 of message m, taken from the registers
+// the bytes pass through — the bytes as they were loaded (over the link
+// for gather, from HBM for scatter), not the bytes that landed; the
+// receiving memory is proven by rocp2p_crc32_msgs / rocp2p_verify.
+// Same descriptors and preconditions as gather/scatter; no byte outside
+// [start, start + msg_bytes) of a message is touched on either side.
+// Stream-ordered, allocate nothing; d_out (n words) is zeroed on
+// `stream`.  grid_cap: 0 = tuned default (128 workgroups of 4 waves, and
+// never above the plain engine's cap), otherwise a lower maximum — a
+// tuning and testing knob.
+hipError_t rocp2p_gather_crc(void* dst_base, const uint64_t* d_dst_offs,
+                             const uint64_t* d_src_addrs, uint64_t msg_bytes,
+                             uint32_t n, uint32_t* d_out, uint32_t grid_cap,
+                             hipStream_t stream);
+hipError_t rocp2p_scatter_crc(const void* src_base,
+                              const uint64_t* d_src_offs,
+                              const uint64_t* d_dst_addrs, uint64_t msg_bytes,
+                              uint32_t n, uint32_t* d_out, uint32_t grid_cap,
+                              hipStream_t stream);
+
 }  // extern "C"

@@ -193,6 +193,8 @@ __global__ void k_msg_engine(uint8_t* __restrict__ region,
 // slice: slicing-by-8.  shift[k]: byte-sliced GF(2) operator "64 B << k
 // follow" (applying a 32x32 GF(2) matrix becomes 4 lookups instead of
 // 32 serial dependent steps).  xpow8: x^(8 * v * 256^j) mod P.
+// shift16: the 16- and 32-byte operators of k_msg_engine_crc, behind
+// the rest so that nothing the older kernels stage has moved.
 // Uploaded by crc_tables_ready(), once per device: holding the same
 // bytes as constant-initialised data of the code object instead cost
 // k_crc32_pages, which stages them 8192 times per GiB, 7-9%
@@ -509,6 +511,171 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
 }
 
 // ---------------------------------------------------------------------
+// Message engine with inline ICRC: moves the batch like k_msg_engine and
+// digests every message from the registers the bytes pass through, the
+// way an HCA checks a packet's ICRC while the data goes by.  The digest
+// is of the bytes AS LOADED (over the link for GATHER); what later sits
+// in HBM is crc32_messages' business.
+//
+// Work split, running CRC, end-of-run shift and the workgroup merge are
+// k_crc32_msgs' (above).  What differs is the chunk layout: a lane of a
+// full 4 KiB chunk holds the 16-byte pieces l, l+64, l+128, l+192, so
+// every wave load/store is one contiguous 1 KiB access — the shape the
+// plain engine's PCIe rate was measured with (crc_page's 64 B per lane
+// would make each wave load 64 separate 16-byte PCIe reads).  Piece
+// q = 64u + l has 1024(3-u) + 16(63-l) bytes of the chunk after it, and
+// shifts commute: a lane Horner-folds its four piece CRCs with the
+// 1 KiB operator (shift[4]), then one log tree over the lanes with the
+// operators 16 B << k (shift16[0..1], shift[0..3]) finishes the chunk.
+// A partial chunk (16..4080 bytes, a multiple of 16) neither loads nor
+// stores a piece at or past the message end; every valid piece is
+// shifted by the bytes that really follow it and the wave XOR-reduces.
+
+// The 40 KiB a workgroup of the inline-ICRC engine keeps in LDS.
+struct icrc_lds {
+  crc_lds t;
+  uint32_t shift16[2][4][256];
+};
+
+// zlib crc32 of one 16-byte piece
+__device__ __forceinline__ uint32_t crc_piece16(const rocp2p_crc_tab256* t,
+                                                const uint4& v) {
+  uint32_t crc = rocp2p_crc_step8(t, 0xFFFFFFFFu, v.x, v.y);
+  return rocp2p_crc_step8(t, crc, v.z, v.w) ^ 0xFFFFFFFFu;
+}
+
+#define ICRC_WAVES 4u
+template <bool GATHER>
+__global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_crc(
+    uint8_t* __restrict__ region, const uint64_t* __restrict__ offs,
+    const uint64_t* __restrict__ addrs, uint64_t msg_bytes, uint64_t cpm,
+    uint64_t total, uint64_t run, uint32_t* __restrict__ out) {
+  __shared__ icrc_lds s;
+  for (uint32_t i = threadIdx.x; i < 2 * 4 * 256; i += blockDim.x)
+    (&s.shift16[0][0][0])[i] = (&c_crc.shift16[0][0][0])[i];
+  crc_stage_tables(s.t);
+
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv = threadIdx.x / WAVE, nwv = blockDim.x / WAVE;
+  const uint64_t wave = (uint64_t)blockIdx.x * nwv + wv;
+  uint64_t c0 = wave * run;
+  if (c0 > total) c0 = total;  // idle wave: empty run, still joins the merge
+  const uint64_t c1 = (total - c0 < run) ? total : c0 + run;
+
+  uint64_t m = 0, ci = 0;
+  // this message on the side that is read and on the side that is written
+  const uint8_t* from = nullptr;
+  uint8_t* to = nullptr;
+  auto open_msg = [&](uint64_t msg) {
+    uint8_t* inside = region + offs[msg];
+    uint8_t* outside = reinterpret_cast<uint8_t*>(addrs[msg]);
+    from = GATHER ? outside : inside;
+    to = GATHER ? inside : outside;
+  };
+  if (c0 < c1) {
+    m = c0 / cpm;
+    ci = c0 - m * cpm;
+    open_msg(m);
+  }
+  uint32_t acc = 0;  // crc of this run's full chunks of message m so far
+  uint32_t pend_f = 0, pend_m = 0;
+
+  for (uint64_t c = c0; c < c1; c++) {
+    const uint64_t pos = ci * PAGE;
+    const uint64_t left = msg_bytes - pos;  // > 0, a multiple of 16
+    const uint4* src = reinterpret_cast<const uint4*>(from + pos);
+    uint4* dst = reinterpret_cast<uint4*>(to + pos);
+    uint64_t done;  // message bytes [.., done) are covered by acc
+    if (left >= PAGE) {
+      uint4 v[4];
+#pragma unroll
+      for (uint32_t u = 0; u < 4; u++) v[u] = src[lane + WAVE * u];
+#pragma unroll
+      for (uint32_t u = 0; u < 4; u++) dst[lane + WAVE * u] = v[u];
+      uint32_t crc = crc_piece16(s.t.slice, v[0]);
+#pragma unroll
+      for (uint32_t u = 1; u < 4; u++)
+        crc = rocp2p_crc_apply(s.t.shift[4], crc) ^
+              crc_piece16(s.t.slice, v[u]);
+      // lane tree: level k merges adjacent spans of 16 B << k
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        uint32_t partner = __shfl_xor(crc, 1u << k, WAVE);
+        bool is_left = ((lane >> k) & 1u) == 0;
+        uint32_t cl = is_left ? crc : partner;
+        uint32_t cr = is_left ? partner : crc;
+        crc = rocp2p_crc_apply(k < 2 ? s.shift16[k] : s.t.shift[k - 2], cl) ^
+              cr;
+      }
+      acc = rocp2p_crc_apply(s.t.shift[5],
+                             rocp2p_crc_apply(s.t.shift[5], acc)) ^ crc;
+      done = pos + PAGE;
+    } else {
+      const uint32_t valid = (uint32_t)left;  // 16..4080
+      const uint32_t nvec = valid / 16;
+      uint32_t x = 0;
+#pragma unroll
+      for (uint32_t u = 0; u < 4; u++) {
+        const uint32_t q = lane + WAVE * u;
+        if (q < nvec) {
+          uint4 v = src[q];
+          dst[q] = v;
+          x ^= rocp2p_crc_mulmod(
+              rocp2p_crc_xpow8(valid - 16 * (q + 1), c_crc.xpow8),
+              crc_piece16(s.t.slice, v));
+        }
+      }
+      for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
+      if (lane == 0) atomicXor(&out[m], x);
+      done = pos;  // acc (if any) still has `valid` bytes after it
+    }
+    const bool msg_end = ci + 1 == cpm;
+    if (msg_end || c + 1 == c1) {
+      if (acc) {  // a zero CRC contributes nothing wherever it sits
+        const uint64_t r = msg_bytes - done;
+        uint32_t f = acc;
+        if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
+        if (msg_end) {
+          if (lane == 0) atomicXor(&out[m], f);
+        } else {
+          pend_f = f;
+          pend_m = (uint32_t)m;
+        }
+      }
+      acc = 0;
+    }
+    if (msg_end) {
+      m++;
+      ci = 0;
+      if (c + 1 < c1) open_msg(m);
+    } else {
+      ci++;
+    }
+  }
+
+  // merge the workgroup's pending shares, as k_crc32_msgs does
+  __syncthreads();
+  uint32_t* s_pend = &s.t.slice[0][0];
+  if (lane == 0) {
+    s_pend[2 * wv] = pend_f;
+    s_pend[2 * wv + 1] = pend_m;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t f = s_pend[0], fm = s_pend[1];
+    for (uint32_t w = 1; w < nwv; w++) {
+      if (s_pend[2 * w + 1] != fm) {
+        if (f) atomicXor(&out[fm], f);
+        f = 0;
+        fm = s_pend[2 * w + 1];
+      }
+      f ^= s_pend[2 * w];
+    }
+    if (f) atomicXor(&out[fm], f);
+  }
+}
+
+// ---------------------------------------------------------------------
 // launchers
 
 static inline uint32_t stream_grid(uint64_t items, uint32_t per_block) {
@@ -633,6 +800,65 @@ static hipError_t crc_tables_ready() {
   e = hipMemcpyToSymbol(HIP_SYMBOL(c_crc), &tables, sizeof(tables));
   ready[dev] = e == hipSuccess;
   return e;
+}
+
+// Inline-ICRC engine launch: 4-wave workgroups, one chunk per wave until
+// the grid is full, longer runs after that.  The grid stays under the
+// plain engine's cap and, measured on MI355X, under 128 workgroups: the
+// fused gather loses to its own outstanding PCIe reads beyond that
+// (1 MiB-class messages: 49.9 GB/s at 512 workgroups, 52.9 at 256, 54.0
+// at 128, 53.6 at 64; the scatter direction does not care).
+// grid_cap != 0 caps the workgroup count further.
+#define ICRC_GRID 128u
+template <bool GATHER>
+static hipError_t msg_engine_crc_launch(void* region, const uint64_t* d_offs,
+                                        const uint64_t* d_addrs,
+                                        uint64_t msg_bytes, uint32_t n,
+                                        uint32_t* d_out, uint32_t grid_cap,
+                                        hipStream_t stream) {
+  if (msg_bytes % 16 || !msg_bytes) return hipErrorInvalidValue;
+  if (!n) return hipSuccess;
+  hipError_t e = crc_tables_ready();
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+  if (e != hipSuccess) return e;
+  uint64_t cpm = msg_bytes / PAGE + (msg_bytes % PAGE != 0);
+  uint64_t total;
+  if (__builtin_mul_overflow(cpm, (uint64_t)n, &total))
+    return hipErrorInvalidValue;
+  const uint64_t W = ICRC_WAVES;
+  uint64_t cap = gather_grid_cap();
+  if (cap > ICRC_GRID) cap = ICRC_GRID;
+  if (grid_cap && grid_cap < cap) cap = grid_cap;
+  uint64_t blocks = (total + W - 1) / W;
+  if (blocks > cap) blocks = cap;
+  uint64_t run = (total + W * blocks - 1) / (W * blocks);
+  hipLaunchKernelGGL(k_msg_engine_crc<GATHER>, dim3((uint32_t)blocks),
+                     dim3(WAVE * ICRC_WAVES), 0, stream, (uint8_t*)region,
+                     d_offs, d_addrs, msg_bytes, cpm, total, run, d_out);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rocp2p_gather_crc(void* dst_base,
+                                        const uint64_t* d_dst_offs,
+                                        const uint64_t* d_src_addrs,
+                                        uint64_t msg_bytes, uint32_t n,
+                                        uint32_t* d_out, uint32_t grid_cap,
+                                        hipStream_t stream) {
+  return msg_engine_crc_launch<true>(dst_base, d_dst_offs, d_src_addrs,
+                                     msg_bytes, n, d_out, grid_cap, stream);
+}
+
+extern "C" hipError_t rocp2p_scatter_crc(const void* src_base,
+                                         const uint64_t* d_src_offs,
+                                         const uint64_t* d_dst_addrs,
+                                         uint64_t msg_bytes, uint32_t n,
+                                         uint32_t* d_out, uint32_t grid_cap,
+                                         hipStream_t stream) {
+  // the scatter instantiation only reads the region
+  return msg_engine_crc_launch<false>(const_cast<void*>(src_base), d_src_offs,
+                                      d_dst_addrs, msg_bytes, n, d_out,
+                                      grid_cap, stream);
 }
 
 extern "C" hipError_t rocp2p_crc32_pages(const void* buf, uint64_t npages,

@@ -13,6 +13,14 @@ side (on-GPU via the CRC/verify kernels when the receiver is HBM) —
 never inside a timed section.  `digest_check(payload)` does the same for
 caller-supplied content: per-message CRC32 digests taken at the sender
 and at the receiver are compared, like a NIC's per-message ICRC.
+
+`icrc=True` (opt-in, backends that support it) checks the measured
+traffic itself: `stamp()` records the CRC32 the sending side holds per
+staging slot (write) or per region message (read), every message moved
+afterwards is digested while it is moved and compared with its stamp,
+and `icrc_stats()` reads the running {"checked", "bad"} counters.  The
+inline digest is of the bytes as the engine loaded them; what landed in
+the receiving memory is still proven by integrity_check/digest_check.
 """
 from __future__ import annotations
 
@@ -21,9 +29,14 @@ import abc
 
 class Transport(abc.ABC):
     name = "base"
+    supports_icrc = False
 
     def __init__(self, msg_bytes: int, region_bytes: int,
-                 inflight: int | None = 8, direction: str = "write", **_):
+                 inflight: int | None = 8, direction: str = "write",
+                 icrc: bool = False, **_):
+        if icrc and not self.supports_icrc:
+            raise NotImplementedError(
+                f"{self.name} transport does not implement icrc=True")
         if region_bytes % msg_bytes:
             raise ValueError("region must be a multiple of msg size")
         if direction not in ("write", "read"):
@@ -34,6 +47,7 @@ class Transport(abc.ABC):
         self.region_bytes = region_bytes
         self.inflight = max(1, min(inflight, region_bytes // msg_bytes))
         self.direction = direction
+        self.icrc = bool(icrc)
 
     # -- data plane ----------------------------------------------------
     @abc.abstractmethod
@@ -64,6 +78,22 @@ class Transport(abc.ABC):
         intact).  Optional: backends without it raise."""
         raise NotImplementedError(
             f"{self.name} transport does not implement digest_check")
+
+    # -- inline ICRC (icrc=True only) ----------------------------------
+    def stamp(self) -> None:
+        """Record the expected CRC32 of what the sending side holds now
+        (staging slots for write, region messages for read).  Messages
+        posted from here on are compared with it while they move; call
+        it again after changing the sender's content.  integrity_check
+        and digest_check rewrite the sender and drop the stamp."""
+        raise NotImplementedError(
+            f"{self.name} transport was not opened with icrc=True")
+
+    def icrc_stats(self) -> dict:
+        """{"checked": messages compared with their stamp so far,
+        "bad": how many of them differed}."""
+        raise NotImplementedError(
+            f"{self.name} transport was not opened with icrc=True")
 
     def _payload_bytes(self, payload):
         """payload as a flat contiguous uint8 numpy array of region_bytes."""

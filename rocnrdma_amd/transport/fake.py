@@ -13,25 +13,61 @@ from .base import Transport
 
 class FakeTransport(Transport):
     name = "fake"
+    supports_icrc = True  # zlib on the host: the sdma logic, CPU tier
 
     def __init__(self, msg_bytes: int, region_bytes: int, **kw):
         super().__init__(msg_bytes, region_bytes, **kw)
         self.staging = np.zeros((self.inflight, msg_bytes), dtype=np.uint8)
         self.region = np.zeros(region_bytes, dtype=np.uint8)
+        if self.icrc:
+            self._expected = None  # per slot (write) / per message (read)
+            self._checked = self._bad = 0
+            self._inline = None  # digests of a running digest_check
 
     def post(self, i: int) -> None:
         slot = self.staging[i % self.inflight]
         off = (i % self.msgs_per_region) * self.msg_bytes
         dst = self.region[off : off + self.msg_bytes]
+        if self.icrc:
+            self._digest(i, slot if self.direction == "write" else dst)
         if self.direction == "write":
             dst[:] = slot
         else:
             slot[:] = dst
 
+    def _digest(self, i: int, src) -> None:
+        """The inline ICRC: digest the bytes being moved, compare with
+        the stamp if there is one."""
+        crc = zlib.crc32(src.tobytes())
+        if self._inline is not None:
+            self._inline.append(crc)
+        if self._expected is not None:
+            k = (i % self.inflight if self.direction == "write"
+                 else i % self.msgs_per_region)
+            self._checked += 1
+            self._bad += int(crc != int(self._expected[k]))
+
     def flush(self) -> None:  # synchronous backend
         pass
 
+    def stamp(self) -> None:
+        if not self.icrc:
+            return super().stamp()
+        if self.direction == "write":
+            self._expected = np.array(
+                [zlib.crc32(s.tobytes()) for s in self.staging], np.uint32)
+        else:
+            self._expected = pattern.crc32_messages_reference(
+                self.region, self.msg_bytes)
+
+    def icrc_stats(self) -> dict:
+        if not self.icrc:
+            return super().icrc_stats()
+        return {"checked": self._checked, "bad": self._bad}
+
     def integrity_check(self, seed: int) -> int:
+        if self.icrc:
+            self._expected = None  # the sender is rewritten below
         ref = pattern.fill_reference(self.region_bytes, seed)
         if self.direction == "write":
             for i in range(self.msgs_per_region):
@@ -59,23 +95,37 @@ class FakeTransport(Transport):
     def digest_check(self, payload) -> int:
         pay = self._payload_bytes(payload)
         n, msg = self.msgs_per_region, self.msg_bytes
-        if self.direction == "write":
-            sent = []
+        if self.icrc:
+            # the region-side digests come from the inline ICRC of the
+            # transfer itself, not from a second pass over the region
+            self._expected = None
+            self._inline = []
+        try:
+            if self.direction == "write":
+                sent = []
+                for i in range(n):
+                    slot = self.staging[i % self.inflight]
+                    slot[:] = pay[i * msg : (i + 1) * msg]
+                    sent.append(zlib.crc32(slot.tobytes()))
+                    self.post(i)
+                self.flush()
+                if self.icrc:
+                    got = np.array(self._inline, np.uint32)
+                else:
+                    got = pattern.crc32_messages_reference(self.region, msg)
+                return int(np.count_nonzero(got != np.array(sent, np.uint32)))
+            # read: load the region, digest it, pull slot by slot
+            self.region[:] = pay
+            if not self.icrc:
+                sent = pattern.crc32_messages_reference(self.region, msg)
+            bad = 0
             for i in range(n):
-                slot = self.staging[i % self.inflight]
-                slot[:] = pay[i * msg : (i + 1) * msg]
-                sent.append(zlib.crc32(slot.tobytes()))
                 self.post(i)
-            self.flush()
-            got = pattern.crc32_messages_reference(self.region, msg)
-            return int(np.count_nonzero(got != np.array(sent, np.uint32)))
-        # read: load the region, digest it, pull slot by slot
-        self.region[:] = pay
-        sent = pattern.crc32_messages_reference(self.region, msg)
-        bad = 0
-        for i in range(n):
-            self.post(i)
-            self.flush()
-            got = zlib.crc32(self.staging[i % self.inflight].tobytes())
-            bad += int(got != int(sent[i]))
-        return bad
+                self.flush()
+                got = zlib.crc32(self.staging[i % self.inflight].tobytes())
+                want = self._inline[i] if self.icrc else int(sent[i])
+                bad += int(got != want)
+            return bad
+        finally:
+            if self.icrc:
+                self._inline = None

@@ -19,6 +19,12 @@ Two engines, mirroring how a NIC actually retires work:
 
 "auto" picks kernel below 8 MiB messages (measured crossover).  Integrity is proven on-GPU
 (verify/CRC kernels) — zero host readback for write direction.
+
+icrc=True (kernel engine only) swaps in the fused engine
+(ops.gather_crc_/scatter_crc_): the launch that moves a batch also
+digests every message, and the digests are compared with the stamped
+expectations on the same stream — each WQE carries a third word for
+that — into two device counters.  No host readback, no extra sync.
 """
 from __future__ import annotations
 
@@ -33,6 +39,7 @@ _STAGING_TARGET = 64 << 20  # pinned staging budget for small messages
 
 class SdmaTransport(Transport):
     name = "sdma"
+    supports_icrc = True
 
     def __init__(self, msg_bytes: int, region_bytes: int, device=None,
                  num_streams: int = 2, engine: str = "auto",
@@ -42,6 +49,12 @@ class SdmaTransport(Transport):
         if engine == "auto":
             engine = "kernel" if msg_bytes < _KERNEL_THRESHOLD else "stream"
         self.engine = engine
+        if kw.get("icrc") and engine != "kernel":
+            raise ValueError(
+                "icrc=True needs the kernel engine: the stream engine "
+                "(explicit, or picked by auto for messages of 8 MiB and "
+                "up) moves data with hipMemcpyAsync, where no kernel "
+                "sees the bytes to digest them")
         if inflight in (None, 0):
             if engine == "kernel":
                 inflight = max(8, min(region_bytes // msg_bytes,
@@ -69,14 +82,28 @@ class SdmaTransport(Transport):
             self._slot_addr = [base + i * msg_bytes
                                for i in range(self.inflight)]
             self._slot_addr_np = np.array(self._slot_addr, dtype=np.int64)
-            # WQE ring: [0] = region offset, [1] = staging address
-            self._desc_pin = torch.empty((2, self.inflight),
+            # WQE ring: [0] = region offset, [1] = staging address; with
+            # icrc [2] = what the digest is compared with: the expected
+            # CRC32 of the slot (write), or the region message whose
+            # stamp stays on the device (read)
+            rows = 3 if self.icrc else 2
+            self._desc_pin = torch.empty((rows, self.inflight),
                                          dtype=torch.int64, pin_memory=True)
             self._desc_np = self._desc_pin.numpy()
-            self._desc_dev = torch.empty((2, self.inflight),
+            self._desc_dev = torch.empty((rows, self.inflight),
                                          dtype=torch.int64,
                                          device=self.device)
             self._pending = 0
+        if self.icrc:
+            self._stamped = False
+            self._exp_slot_np = None  # write: int32-wrapped CRC per slot
+            self._exp_dev = None      # read: int32 CRC per region message
+            self._icrc_dev = torch.zeros(2, dtype=torch.int64,
+                                         device=self.device)  # checked, bad
+            self._last_digests = None  # of the last flushed batch
+            # the counters were zeroed on the caller's stream; flush()
+            # updates them on its own
+            torch.cuda.synchronize(self.device)
 
     # -- data plane ----------------------------------------------------
     def post(self, i: int) -> None:
@@ -88,6 +115,10 @@ class SdmaTransport(Transport):
             k = self._pending
             self._desc_np[0, k] = off
             self._desc_np[1, k] = self._slot_addr[slot]
+            if self.icrc and self._stamped:
+                self._desc_np[2, k] = (
+                    self._exp_slot_np[slot] if self.direction == "write"
+                    else i % self.msgs_per_region)
             self._pending = k + 1
             return
         stream = self.streams[i % len(self.streams)]
@@ -118,6 +149,11 @@ class SdmaTransport(Transport):
                 (idx % self.msgs_per_region) * self.msg_bytes
             self._desc_np[1, k:k + take] = \
                 self._slot_addr_np[idx % self.inflight]
+            if self.icrc and self._stamped:
+                self._desc_np[2, k:k + take] = (
+                    self._exp_slot_np[idx % self.inflight]
+                    if self.direction == "write"
+                    else idx % self.msgs_per_region)
             self._pending = k + take
             done += take
 
@@ -132,7 +168,9 @@ class SdmaTransport(Transport):
                 with torch.cuda.stream(stream):
                     self._desc_dev[:, :n].copy_(self._desc_pin[:, :n],
                                                 non_blocking=True)
-                    if self.direction == "write":
+                    if self.icrc:
+                        self._flush_icrc(n)
+                    elif self.direction == "write":
                         ops.gather_(self.region, self._desc_dev[0, :n],
                                     self._desc_dev[1, :n], self.msg_bytes)
                     else:
@@ -143,10 +181,56 @@ class SdmaTransport(Transport):
         for s in self.streams:
             s.synchronize()
 
+    def _flush_icrc(self, n: int) -> None:
+        """Fused engine + compare, on the current (flush) stream."""
+        from .. import ops
+
+        engine = (ops.gather_crc_ if self.direction == "write"
+                  else ops.scatter_crc_)
+        dig = engine(self.region, self._desc_dev[0, :n],
+                     self._desc_dev[1, :n], self.msg_bytes)
+        self._last_digests = dig
+        if not self._stamped:
+            return
+        field = self._desc_dev[2, :n]
+        exp = field if self.direction == "write" else self._exp_dev[field]
+        self._icrc_dev[0].add_(n)
+        self._icrc_dev[1].add_((dig != exp).sum())
+
+    def stamp(self) -> None:
+        if not self.icrc:
+            return super().stamp()
+        import zlib
+
+        import numpy as np
+
+        from .. import ops
+
+        self.flush()
+        if self.direction == "write":
+            crcs = np.array([zlib.crc32(s.numpy()) for s in self.staging],
+                            dtype=np.uint32)
+            # as the int32 the engine returns, widened to the WQE word
+            self._exp_slot_np = crcs.view(np.int32).astype(np.int64)
+        else:
+            self._exp_dev = ops.crc32_messages(self.region, self.msg_bytes)
+            # taken on the caller's stream; flush() works on its own
+            torch.cuda.synchronize(self.device)
+        self._stamped = True
+
+    def icrc_stats(self) -> dict:
+        if not self.icrc:
+            return super().icrc_stats()
+        self.flush()
+        checked, bad = self._icrc_dev.tolist()
+        return {"checked": checked, "bad": bad}
+
     # -- integrity plane ----------------------------------------------
     def integrity_check(self, seed: int) -> int:
         from .. import ops
 
+        if self.icrc:
+            self._stamped = False  # the sender is rewritten below
         ref = pattern.fill_reference(self.region_bytes, seed)
         ref_t = torch.from_numpy(ref.copy())
         if self.direction == "write":
@@ -193,6 +277,8 @@ class SdmaTransport(Transport):
         pay = self._payload_bytes(payload)
         pay_t = torch.from_numpy(pay)
         n, msg = self.msgs_per_region, self.msg_bytes
+        if self.icrc:
+            return self._digest_check_icrc(pay_t)
         if self.direction == "write":
             sent = np.empty(n, dtype=np.uint32)
             i = 0
@@ -225,6 +311,41 @@ class SdmaTransport(Transport):
                 bad += int(got != int(sent[j]))
             i += burst
         return bad
+
+    def _digest_check_icrc(self, pay_t) -> int:
+        """digest_check with the HBM-side digests taken by the fused
+        engine while it moves each burst — no second pass over the
+        region.  The host side is digested with zlib as before."""
+        import zlib
+
+        import numpy as np
+
+        n, msg = self.msgs_per_region, self.msg_bytes
+        write = self.direction == "write"
+        self._stamped = False  # the sender is rewritten below
+        if not write:
+            self.region.copy_(pay_t)
+            torch.cuda.synchronize(self.device)
+        host = np.empty(n, dtype=np.uint32)
+        inline = []
+        i = 0
+        while i < n:
+            burst = min(self.inflight, n - i)
+            for j in range(i, i + burst):
+                if write:
+                    slot = self.staging[j % self.inflight]
+                    slot.copy_(pay_t[j * msg:(j + 1) * msg])
+                    host[j] = zlib.crc32(slot.numpy())
+                self.post(j)
+            self.flush()  # slots reused next burst: must complete
+            inline.append(self._last_digests)
+            if not write:
+                for j in range(i, i + burst):
+                    host[j] = zlib.crc32(
+                        self.staging[j % self.inflight].numpy())
+            i += burst
+        got = torch.cat(inline).cpu().numpy().view(np.uint32)
+        return int(np.count_nonzero(got != host))
 
     def close(self) -> None:
         self.flush()
