@@ -4,7 +4,7 @@ stability tier for production deployment (run for minutes/hours on a
 deploy candidate; the GPU test tier runs a short bounded pass).
 
 CLI: python -m rocnrdma_amd.harness.soak [--secs 30] [--transport auto]
-                                         [--audit pattern|crc]
+                                         [--audit pattern|crc] [--mixed]
 Exit nonzero on any integrity failure.
 """
 from __future__ import annotations
@@ -16,16 +16,41 @@ import time
 SIZES = [4 << 10, 16 << 10, 64 << 10, 256 << 10, 1 << 20, 4 << 20]
 
 
+def mixed_lens(rng: random.Random, n: int, msg: int):
+    """n seeded message lengths for a slot of msg bytes: multiples of 16
+    in [0, msg], with mass on 0, 16, msg and just around the 4096-byte
+    chunk boundaries, where the engine changes path."""
+    import numpy as np
+
+    g = np.random.default_rng(rng.getrandbits(32))
+    lens = g.integers(0, msg // 16 + 1, n, dtype=np.int64) * 16
+    kind = g.random(n)
+    lens[kind < 0.10] = 0
+    lens[(kind >= 0.10) & (kind < 0.20)] = 16
+    lens[(kind >= 0.20) & (kind < 0.35)] = msg
+    edge = (kind >= 0.35) & (kind < 0.55)
+    near = (g.integers(1, max(msg // 4096, 1) + 1, n, dtype=np.int64) * 4096
+            + g.integers(-1, 2, n, dtype=np.int64) * 16)
+    lens[edge] = np.clip(near, 0, msg)[edge]
+    return lens
+
+
 def run_soak(transport: str = "auto", secs: float = 10.0,
              region_bytes: int = 256 << 20, seed: int = 1234,
              device=None, metrics=None, audit: str = "pattern",
-             icrc: bool = False) -> dict:
+             icrc: bool = False, mixed: bool = False) -> dict:
     """audit="pattern": splitmix64 pattern + integrity_check (default).
     audit="crc": a seeded random payload per cycle through digest_check
     (per-message CRC32, content-independent).
     icrc=True: the burst phase runs on a patterned, stamped sender with
     every message's CRC32 checked inline; a cycle with a bad message is
-    a failure, and the stats gain icrc_checked / icrc_bad."""
+    a failure, and the stats gain icrc_checked / icrc_bad.
+    mixed=True: every cycle opens the transport with var_len=True at a
+    slot size from SIZES, posts its bursts with seeded random lengths
+    (mixed_lens) and audits with digest_check(payload, lens), slack
+    included; msgs and bytes count what was actually moved.  A stamp
+    cannot serve variable lengths, so with icrc=True the inline digests
+    are used by the audit only."""
     from rocnrdma_amd.harness.sweep import pattern_sender
     from rocnrdma_amd.transport import get_transport
 
@@ -44,6 +69,8 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
     if icrc:
         extra["icrc"] = True
         stats.update(icrc_checked=0, icrc_bad=0)
+    if mixed:
+        extra["var_len"] = True
     while time.monotonic() < t_end:
         msg = rng.choice(SIZES)
         direction = rng.choice(["write", "read"])
@@ -51,6 +78,17 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
         tp = get_transport(transport, msg_bytes=msg, region_bytes=region,
                            direction=direction, device=device, **extra)
         try:
+            if mixed:
+                moved, msgs, bad = _mixed_cycle(tp, rng, region)
+                stats["audits"] += 1
+                if bad:
+                    stats["failures"] += 1
+                stats["msgs"] += msgs
+                stats["bytes"] += moved
+                stats["cycles"] += 1
+                metrics.observe_bytes(direction, moved, msgs)
+                metrics.observe_audit(ok=bad == 0)
+                continue
             if icrc:
                 pattern_sender(tp, seed=rng.getrandbits(32))
                 tp.stamp()
@@ -93,6 +131,26 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
     return stats
 
 
+def _mixed_cycle(tp, rng: random.Random, region: int):
+    """One mixed-length cycle on an open var_len transport: (bytes
+    moved, messages moved, bad messages of the audit)."""
+    import numpy as np
+
+    moved = posted = 0
+    for _ in range(rng.randint(1, 4)):
+        burst = rng.randint(1, max(2, tp.inflight))
+        lens = mixed_lens(rng, burst, tp.msg_bytes)
+        tp.post_many(posted, burst, lens)
+        posted += burst
+        moved += int(lens.sum())
+        tp.flush()
+    payload = np.random.default_rng(rng.getrandbits(32)).integers(
+        0, 256, region, dtype=np.uint8)
+    lens = mixed_lens(rng, tp.msgs_per_region, tp.msg_bytes)
+    bad = tp.digest_check(payload, lens)
+    return (moved + int(lens.sum()), posted + tp.msgs_per_region, bad)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--secs", type=float, default=30.0)
@@ -106,6 +164,10 @@ def main():
     ap.add_argument("--icrc", action="store_true",
                     help="run the burst phase stamped, every message's "
                          "CRC32 checked inline")
+    ap.add_argument("--mixed", action="store_true",
+                    help="variable-length traffic: var_len transport, "
+                         "seeded random lengths per message, audited "
+                         "with digest_check(payload, lens)")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="expose Prometheus metrics on this port")
     args = ap.parse_args()
@@ -114,7 +176,7 @@ def main():
     metrics = TransferMetrics(port=args.metrics_port or None)
     stats = run_soak(args.transport, args.secs, args.region_bytes,
                      args.seed, metrics=metrics, audit=args.audit,
-                     icrc=args.icrc)
+                     icrc=args.icrc, mixed=args.mixed)
     print(stats)
     raise SystemExit(1 if stats["failures"] else 0)
 

@@ -107,6 +107,41 @@ def scatter_crc_(region: torch.Tensor, src_offs: torch.Tensor,
                                    grid_cap)
 
 
+def gather_v_(region: torch.Tensor, dst_offs: torch.Tensor,
+              src_addrs: torch.Tensor, lens: torch.Tensor, *,
+              max_msg_bytes: int = 0, crc: bool = False,
+              grid_cap: int = 0) -> torch.Tensor | None:
+    """gather_ for a batch whose messages carry their own lengths: lens
+    is a contiguous int64 GPU tensor[n] of byte counts, multiples of 16,
+    0 allowed (nothing moved, digest 0).  Returns None, or with crc=True
+    the inline ICRC as gather_crc_ does (int32 tensor[n], no sync).
+    max_msg_bytes is an upper bound of the lengths if the caller knows
+    one (0 = unknown); it only sizes the grid, results do not depend on
+    it.  grid_cap as for gather_crc_."""
+    return _require().gather_v_(region, dst_offs, src_addrs, lens,
+                                max_msg_bytes, crc, grid_cap)
+
+
+def scatter_v_(region: torch.Tensor, src_offs: torch.Tensor,
+               dst_addrs: torch.Tensor, lens: torch.Tensor, *,
+               max_msg_bytes: int = 0, crc: bool = False,
+               grid_cap: int = 0) -> torch.Tensor | None:
+    """scatter_ for per-message lengths; see gather_v_."""
+    return _require().scatter_v_(region, src_offs, dst_addrs, lens,
+                                 max_msg_bytes, crc, grid_cap)
+
+
+def crc32_messages_v(region: torch.Tensor, offs: torch.Tensor,
+                     lens: torch.Tensor, *, max_msg_bytes: int = 0,
+                     grid_cap: int = 0) -> torch.Tensor:
+    """zlib-compatible CRC32 of region[offs[m] : offs[m] + lens[m]] for
+    every m; int32 tensor[n] on GPU, no sync.  offs are 16-byte aligned,
+    lens are any byte counts (0 -> 0).  max_msg_bytes and grid_cap as
+    for gather_v_."""
+    return _require().crc32_messages_v(region, offs, lens, max_msg_bytes,
+                                       grid_cap)
+
+
 def dmabuf_fd(buf: torch.Tensor) -> int:
     """Export an HBM tensor as a dmabuf fd (ibv_reg_dmabuf_mr's GPU
     half). Caller must os.close() the fd."""

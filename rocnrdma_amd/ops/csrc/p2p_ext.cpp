@@ -191,6 +191,96 @@ torch::Tensor scatter_crc_(torch::Tensor region, torch::Tensor src_offs,
                         dst_addrs, msg_bytes, grid_cap);
 }
 
+// The per-message-length forms: same checks, plus the length tensor;
+// the n + 1 words of scan scratch and the digests are torch tensors, so
+// the caching allocator keeps them alive until the stream has used them.
+struct VarLenArgs {
+  int64_t n;
+  torch::Tensor cstart;
+  VarLenArgs(const char* who, const torch::Tensor& region,
+             const torch::Tensor& offs, const torch::Tensor* addrs,
+             const torch::Tensor& lens, int64_t max_msg_bytes,
+             int64_t grid_cap) {
+    check_align16(region, who);
+    check_u64_dev(offs, who);
+    if (addrs) check_u64_dev(*addrs, who);
+    check_u64_dev(lens, who);
+    n = offs.numel();
+    TORCH_CHECK(lens.numel() == n && (!addrs || addrs->numel() == n), who,
+                ": n mismatch");
+    TORCH_CHECK(offs.device() == region.device() &&
+                    lens.device() == region.device() &&
+                    (!addrs || addrs->device() == region.device()),
+                who, ": descriptors must live on the region's device");
+    TORCH_CHECK(n < (1LL << 32), who, ": too many messages");
+    TORCH_CHECK(max_msg_bytes >= 0, who, ": max_msg_bytes out of range");
+    TORCH_CHECK(grid_cap >= 0 && grid_cap <= 0xffffffffLL, who,
+                ": grid_cap out of range");
+    cstart = torch::empty(
+        {n + 1}, torch::dtype(torch::kInt64).device(region.device()));
+  }
+};
+
+template <typename Launch>
+c10::optional<torch::Tensor> msg_engine_v(const char* who, Launch launch,
+                                          torch::Tensor region,
+                                          torch::Tensor offs,
+                                          torch::Tensor addrs,
+                                          torch::Tensor lens,
+                                          int64_t max_msg_bytes, bool crc,
+                                          int64_t grid_cap) {
+  OnDeviceOf dev(region, who);
+  VarLenArgs a(who, region, offs, &addrs, lens, max_msg_bytes, grid_cap);
+  c10::optional<torch::Tensor> out;
+  if (crc)
+    out = torch::empty({a.n},
+                       torch::dtype(torch::kInt32).device(region.device()));
+  HIP_OK(launch(region.data_ptr(), (const uint64_t*)offs.data_ptr<int64_t>(),
+                (const uint64_t*)addrs.data_ptr<int64_t>(),
+                (const uint64_t*)lens.data_ptr<int64_t>(), (uint32_t)a.n,
+                (uint64_t)max_msg_bytes,
+                (uint64_t*)a.cstart.data_ptr<int64_t>(),
+                crc ? (uint32_t*)out->data_ptr<int32_t>() : nullptr,
+                (uint32_t)grid_cap, dev.stream));
+  return out;
+}
+
+c10::optional<torch::Tensor> gather_v_(torch::Tensor region,
+                                       torch::Tensor dst_offs,
+                                       torch::Tensor src_addrs,
+                                       torch::Tensor lens,
+                                       int64_t max_msg_bytes, bool crc,
+                                       int64_t grid_cap) {
+  return msg_engine_v("gather_v_", rocp2p_gather_v, region, dst_offs,
+                      src_addrs, lens, max_msg_bytes, crc, grid_cap);
+}
+
+c10::optional<torch::Tensor> scatter_v_(torch::Tensor region,
+                                        torch::Tensor src_offs,
+                                        torch::Tensor dst_addrs,
+                                        torch::Tensor lens,
+                                        int64_t max_msg_bytes, bool crc,
+                                        int64_t grid_cap) {
+  return msg_engine_v("scatter_v_", rocp2p_scatter_v, region, src_offs,
+                      dst_addrs, lens, max_msg_bytes, crc, grid_cap);
+}
+
+torch::Tensor crc32_messages_v(torch::Tensor region, torch::Tensor offs,
+                               torch::Tensor lens, int64_t max_msg_bytes,
+                               int64_t grid_cap) {
+  OnDeviceOf dev(region, "crc32_messages_v");
+  VarLenArgs a("crc32_messages_v", region, offs, nullptr, lens,
+               max_msg_bytes, grid_cap);
+  auto out = torch::empty({a.n},
+                          torch::dtype(torch::kInt32).device(region.device()));
+  HIP_OK(rocp2p_crc32_msgs_v(
+      region.data_ptr(), (const uint64_t*)offs.data_ptr<int64_t>(),
+      (const uint64_t*)lens.data_ptr<int64_t>(), (uint32_t)a.n,
+      (uint64_t)max_msg_bytes, (uint64_t*)a.cstart.data_ptr<int64_t>(),
+      (uint32_t*)out.data_ptr<int32_t>(), (uint32_t)grid_cap, dev.stream));
+  return out;
+}
+
 void copy_(torch::Tensor dst, torch::Tensor src) {
   OnDeviceOf dev(dst, "copy_");
   check_buf(src, "copy_");
@@ -250,6 +340,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "scatter_ plus one zlib CRC32 per message, taken in the same pass",
         py::arg("region"), py::arg("src_offs"), py::arg("dst_addrs"),
         py::arg("msg_bytes"), py::arg("grid_cap") = 0);
+  m.def("gather_v_", &gather_v_,
+        "gather_ for per-message lengths; crc=True adds the inline ICRC",
+        py::arg("region"), py::arg("dst_offs"), py::arg("src_addrs"),
+        py::arg("lens"), py::arg("max_msg_bytes") = 0,
+        py::arg("crc") = false, py::arg("grid_cap") = 0);
+  m.def("scatter_v_", &scatter_v_,
+        "scatter_ for per-message lengths; crc=True adds the inline ICRC",
+        py::arg("region"), py::arg("src_offs"), py::arg("dst_addrs"),
+        py::arg("lens"), py::arg("max_msg_bytes") = 0,
+        py::arg("crc") = false, py::arg("grid_cap") = 0);
+  m.def("crc32_messages_v", &crc32_messages_v,
+        "zlib CRC32 of each message base[offs[m], offs[m] + lens[m])",
+        py::arg("region"), py::arg("offs"), py::arg("lens"),
+        py::arg("max_msg_bytes") = 0, py::arg("grid_cap") = 0);
   m.def("dmabuf_fd", &dmabuf_fd,
         "export an HBM tensor range as a dmabuf fd (caller closes)");
 }

@@ -92,4 +92,43 @@ hipError_t rocp2p_scatter_crc(const void* src_base,
                               uint32_t n, uint32_t* d_out, uint32_t grid_cap,
                               hipStream_t stream);
 
+// Per-message lengths: the same engine, digest and inline ICRC for
+// batches in which message m has d_lens[m] bytes (device u64 array of n
+// entries; work split and cursor: p2p_varlen.h).  0 is legal, as a
+// zero-length RDMA write is: nothing is touched and the digest is 0,
+// zlib's crc32(b"").  For the engine the lengths are multiples of 16 and
+// offsets/addresses 16-byte aligned, as above; crc32_msgs_v takes any
+// byte length and never loads a byte at or past a message's end.  The
+// descriptors on the device are trusted like d_offs / d_addrs are.
+// Stream-ordered, allocate nothing, no host synchronise: a one-workgroup
+// scan kernel writes the chunk prefix sums into d_cstart (n + 1 words of
+// caller-provided scratch) and the main kernel follows on the same
+// stream.  The host never learns the sum of the lengths.
+// max_msg_bytes: an upper bound the caller knows (the slot size), 0 =
+// unknown.  It only sizes the grid; results do not depend on it.
+// d_out: n digests (zeroed on `stream`); for the engine it may be null:
+// no ICRC, no tables staged, no CRC work.
+// grid_cap: 0 = the default of the uniform counterpart, otherwise a
+// lower maximum number of workgroups.
+// hipErrorInvalidValue: null d_cstart, base not 16-byte aligned.
+// n == 0 is a no-op.  No byte outside [start, start + len) of any
+// message is loaded or stored on either side.
+hipError_t rocp2p_gather_v(void* dst_base, const uint64_t* d_dst_offs,
+                           const uint64_t* d_src_addrs,
+                           const uint64_t* d_lens, uint32_t n,
+                           uint64_t max_msg_bytes, uint64_t* d_cstart,
+                           uint32_t* d_out, uint32_t grid_cap,
+                           hipStream_t stream);
+hipError_t rocp2p_scatter_v(const void* src_base, const uint64_t* d_src_offs,
+                            const uint64_t* d_dst_addrs,
+                            const uint64_t* d_lens, uint32_t n,
+                            uint64_t max_msg_bytes, uint64_t* d_cstart,
+                            uint32_t* d_out, uint32_t grid_cap,
+                            hipStream_t stream);
+hipError_t rocp2p_crc32_msgs_v(const void* base, const uint64_t* d_offs,
+                               const uint64_t* d_lens, uint32_t n,
+                               uint64_t max_msg_bytes, uint64_t* d_cstart,
+                               uint32_t* d_out, uint32_t grid_cap,
+                               hipStream_t stream);
+
 }  // extern "C"

@@ -29,6 +29,7 @@
 #include "p2p_kernels.h"
 #include "p2p_crc.h"
 #include "p2p_pattern.h"
+#include "p2p_varlen.h"
 
 #define WAVE 64u
 #define PAGE 4096u
@@ -159,7 +160,9 @@ __global__ void k_copy_t(uint4_cv* __restrict__ dst,
 // host-pinned staging straight over PCIe (fine-grained zero-copy) and
 // store to the HBM region, 16 B/lane, many messages per launch — so the
 // small-message lines of the ib_write_bw sweep are PCIe-bound, not
-// launch-bound.  msg_bytes is uniform per batch (transport invariant).
+// launch-bound.  msg_bytes is uniform per batch in this kernel and in
+// k_msg_engine_crc; batches whose messages carry their own lengths go
+// through k_msg_engine_v (below).
 
 // Message m lives at region + offs[m] on one side and at the absolute
 // address addrs[m] on the other; GATHER copies addrs -> region, scatter
@@ -676,6 +679,305 @@ __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_crc(
 }
 
 // ---------------------------------------------------------------------
+// Variable-length batches: every message carries its own byte count
+// (lens[m], device memory, 0 allowed), as every verbs work request does.
+// The unit of work is still the 4 KiB chunk, numbered message-major, and
+// each wave still owns a contiguous run of chunks; what changes is that
+// chunks-per-message varies, so "chunk / cpm" is gone.  k_vl_scan first
+// writes cstart[m] = chunks before message m and cstart[n] = the total
+// (p2p_varlen.h); the main kernels read the total from there — the host
+// never learns it — derive their run length from it, find the message of
+// their first chunk with ONE binary search of cstart and then only step
+// forward.  Zero-length messages have an empty chunk range: the cursor
+// steps over them and they never reach a load, a store or an atomic
+// (their digest is the 0 the launcher wrote, zlib's crc32(b"")).
+// 16-byte and multi-MiB messages side by side cost what their chunks
+// cost: a run boundary may fall anywhere, inside a big message or after
+// any number of tiny ones.
+
+// One workgroup of 16 waves; wave w owns a contiguous segment of the
+// messages (a whole number of 64-message tiles, so any n fits and every
+// tile is one coalesced 512-byte access).  Pass 1 sums the segment, one
+// barrier hands the 16 sums over, pass 2 walks the segment tile by tile
+// with a wave scan and a running carry — no barrier inside either loop.
+#define VL_SCAN_THREADS 1024u
+__global__ void __launch_bounds__(VL_SCAN_THREADS) k_vl_scan(
+    const uint64_t* __restrict__ lens, uint32_t n,
+    uint64_t* __restrict__ cstart) {
+  __shared__ uint64_t s_wave[VL_SCAN_THREADS / WAVE];
+  const uint32_t lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const uint64_t per =
+      ((uint64_t)n + VL_SCAN_THREADS - 1) / VL_SCAN_THREADS * WAVE;
+  const uint64_t b = min(wv * per, (uint64_t)n);
+  const uint64_t e = min(b + per, (uint64_t)n);
+  uint64_t sum = 0;
+  for (uint64_t i = b + lane; i < e; i += WAVE)
+    sum += rocp2p_vl_chunks(lens[i]);
+  for (uint32_t o = WAVE / 2; o; o >>= 1) sum += __shfl_xor(sum, o, WAVE);
+  if (lane == 0) s_wave[wv] = sum;
+  __syncthreads();
+  uint64_t at = 0;  // chunks before the tile at hand
+  for (uint32_t w = 0; w < wv; w++) at += s_wave[w];
+  for (uint64_t i0 = b; i0 < e; i0 += WAVE) {  // uniform trip count
+    const uint64_t i = i0 + lane;
+    const uint64_t k = i < e ? rocp2p_vl_chunks(lens[i]) : 0;
+    uint64_t inc = k;  // inclusive scan over the tile
+    for (uint32_t o = 1; o < WAVE; o <<= 1) {
+      uint64_t v = __shfl_up(inc, o, WAVE);
+      if (lane >= o) inc += v;
+    }
+    if (i < e) cstart[i] = at + inc - k;
+    at += __shfl(inc, WAVE - 1, WAVE);
+  }
+  // the last wave's segment ends at n: its carry is the total
+  if (threadIdx.x == VL_SCAN_THREADS - 1) cstart[n] = at;
+}
+
+// zlib crc32 of a full 4 KiB chunk held the engine's way (lane l: pieces
+// l, l+64, l+128, l+192), in every lane: k_msg_engine_crc's algebra.
+__device__ __forceinline__ uint32_t icrc_chunk_full(const icrc_lds& s,
+                                                    const uint4& v0,
+                                                    const uint4& v1,
+                                                    const uint4& v2,
+                                                    const uint4& v3,
+                                                    uint32_t lane) {
+  uint32_t crc = crc_piece16(s.t.slice, v0);
+  crc = rocp2p_crc_apply(s.t.shift[4], crc) ^ crc_piece16(s.t.slice, v1);
+  crc = rocp2p_crc_apply(s.t.shift[4], crc) ^ crc_piece16(s.t.slice, v2);
+  crc = rocp2p_crc_apply(s.t.shift[4], crc) ^ crc_piece16(s.t.slice, v3);
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    uint32_t partner = __shfl_xor(crc, 1u << k, WAVE);
+    bool is_left = ((lane >> k) & 1u) == 0;
+    uint32_t cl = is_left ? crc : partner;
+    uint32_t cr = is_left ? partner : crc;
+    crc = rocp2p_crc_apply(k < 2 ? s.shift16[k] : s.t.shift[k - 2], cl) ^ cr;
+  }
+  return crc;
+}
+
+// Merge the pending shares (runs that ended inside a message) of a
+// workgroup's waves: adjacent waves own adjacent runs, so equal targets
+// are adjacent.  s_pend: 2 * nwv words of LDS that are dead by now; the
+// caller has passed the barrier that says so.
+__device__ __forceinline__ void vl_merge_pending(uint32_t* s_pend,
+                                                 uint32_t lane, uint32_t wv,
+                                                 uint32_t nwv, uint32_t pend_f,
+                                                 uint32_t pend_m,
+                                                 uint32_t* __restrict__ out) {
+  if (lane == 0) {
+    s_pend[2 * wv] = pend_f;
+    s_pend[2 * wv + 1] = pend_m;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t f = s_pend[0], fm = s_pend[1];
+    for (uint32_t w = 1; w < nwv; w++) {
+      if (s_pend[2 * w + 1] != fm) {
+        if (f) atomicXor(&out[fm], f);
+        f = 0;
+        fm = s_pend[2 * w + 1];
+      }
+      f ^= s_pend[2 * w];
+    }
+    if (f) atomicXor(&out[fm], f);
+  }
+}
+
+// The plain form keeps nothing in LDS.
+template <bool ICRC>
+struct vl_engine_lds {};
+template <>
+struct vl_engine_lds<true> {
+  icrc_lds t;
+};
+
+// The message engine for per-message lengths (multiples of 16), with
+// (ICRC) or without the inline digest: one kernel, so both forms move
+// bytes the same way — 1 KiB-contiguous wave accesses, lane l holding
+// pieces l, l+64, l+128, l+192 of a chunk.  Without ICRC no table is
+// staged and no CRC work is done.  The wave index is made provably
+// uniform, so the cursor and the descriptors it loads live in SGPRs.
+template <bool GATHER, bool ICRC>
+__global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_v(
+    uint8_t* __restrict__ region, const uint64_t* __restrict__ offs,
+    const uint64_t* __restrict__ addrs, const uint64_t* __restrict__ lens,
+    const uint64_t* __restrict__ cstart, uint32_t n,
+    uint32_t* __restrict__ out) {
+  __shared__ vl_engine_lds<ICRC> s;
+  if constexpr (ICRC) {
+    for (uint32_t i = threadIdx.x; i < 2 * 4 * 256; i += blockDim.x)
+      (&s.t.shift16[0][0][0])[i] = (&c_crc.shift16[0][0][0])[i];
+    crc_stage_tables(s.t.t);
+  }
+
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv =
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const uint32_t nwv = blockDim.x / WAVE;
+  uint64_t c0, c1;
+  rocp2p_vl_run(cstart[n], (uint64_t)gridDim.x * nwv,
+                (uint64_t)blockIdx.x * nwv + wv, &c0, &c1);
+
+  rocp2p_vl_cursor cur = {0, 0, 0, 0};
+  // this message on the side that is read and on the side that is written
+  const uint8_t* from = nullptr;
+  uint8_t* to = nullptr;
+  auto open_msg = [&](uint64_t msg) {
+    uint8_t* inside = region + offs[msg];
+    uint8_t* outside = reinterpret_cast<uint8_t*>(addrs[msg]);
+    from = GATHER ? outside : inside;
+    to = GATHER ? inside : outside;
+  };
+  if (c0 < c1) {
+    rocp2p_vl_seek(&cur, cstart, lens, n, c0);
+    open_msg(cur.m);
+  }
+  uint32_t acc = 0;  // crc of this run's full chunks of message m so far
+  uint32_t pend_f = 0, pend_m = 0;
+
+  for (uint64_t c = c0; c < c1; c++) {
+    const uint64_t pos = cur.ci * PAGE;
+    const uint64_t left = cur.len - pos;  // > 0, a multiple of 16
+    const uint4* src = reinterpret_cast<const uint4*>(from + pos);
+    uint4* dst = reinterpret_cast<uint4*>(to + pos);
+    uint64_t done;  // message bytes [.., done) are covered by acc
+    if (left >= PAGE) {
+      // four named registers, not an array: the plain form would
+      // otherwise get the array promoted to LDS
+      const uint4 v0 = src[lane], v1 = src[lane + WAVE];
+      const uint4 v2 = src[lane + 2 * WAVE], v3 = src[lane + 3 * WAVE];
+      dst[lane] = v0;
+      dst[lane + WAVE] = v1;
+      dst[lane + 2 * WAVE] = v2;
+      dst[lane + 3 * WAVE] = v3;
+      if constexpr (ICRC)
+        acc = rocp2p_crc_apply(s.t.t.shift[5],
+                               rocp2p_crc_apply(s.t.t.shift[5], acc)) ^
+              icrc_chunk_full(s.t, v0, v1, v2, v3, lane);
+      done = pos + PAGE;
+    } else {
+      const uint32_t valid = (uint32_t)left;  // 16..4080
+      const uint32_t nvec = valid / 16;
+      uint32_t x = 0;
+#pragma unroll
+      for (uint32_t u = 0; u < 4; u++) {
+        const uint32_t q = lane + WAVE * u;
+        if (q < nvec) {
+          uint4 v = src[q];
+          dst[q] = v;
+          if constexpr (ICRC)
+            x ^= rocp2p_crc_mulmod(
+                rocp2p_crc_xpow8(valid - 16 * (q + 1), c_crc.xpow8),
+                crc_piece16(s.t.t.slice, v));
+        }
+      }
+      if constexpr (ICRC) {
+        for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
+        if (lane == 0) atomicXor(&out[cur.m], x);
+      }
+      done = pos;  // acc (if any) still has `valid` bytes after it
+    }
+    if constexpr (ICRC) {
+      const bool msg_end = cur.ci + 1 == cur.cpm;
+      if (msg_end || c + 1 == c1) {
+        if (acc) {  // a zero CRC contributes nothing wherever it sits
+          const uint64_t r = cur.len - done;
+          uint32_t f = acc;
+          if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
+          if (msg_end) {
+            if (lane == 0) atomicXor(&out[cur.m], f);
+          } else {
+            pend_f = f;
+            pend_m = (uint32_t)cur.m;
+          }
+        }
+        acc = 0;
+      }
+    }
+    if (c + 1 < c1 && rocp2p_vl_next(&cur, cstart, lens)) open_msg(cur.m);
+  }
+
+  if constexpr (ICRC) {
+    __syncthreads();  // the tables are dead: their first words hand off
+    vl_merge_pending(&s.t.t.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
+  }
+}
+
+// k_crc32_msgs for per-message lengths (any byte count, 0 included):
+// message m is base[offs[m], offs[m] + lens[m]).
+__global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs_v(
+    const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
+    const uint64_t* __restrict__ lens, const uint64_t* __restrict__ cstart,
+    uint32_t n, uint32_t* __restrict__ out) {
+  __shared__ crc_lds s;
+  crc_stage_tables(s);
+
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv =
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const uint32_t nwv = blockDim.x / WAVE;
+  uint64_t c0, c1;
+  rocp2p_vl_run(cstart[n], (uint64_t)gridDim.x * nwv,
+                (uint64_t)blockIdx.x * nwv + wv, &c0, &c1);
+
+  rocp2p_vl_cursor cur = {0, 0, 0, 0};
+  const uint8_t* mp = base;
+  if (c0 < c1) {
+    rocp2p_vl_seek(&cur, cstart, lens, n, c0);
+    mp = base + offs[cur.m];
+  }
+  uint32_t acc = 0;  // crc of this run's full chunks of message m so far
+  uint32_t pend_f = 0, pend_m = 0;
+
+  for (uint64_t c = c0; c < c1; c++) {
+    const uint64_t pos = cur.ci * PAGE;
+    const uint64_t left = cur.len - pos;  // > 0
+    const uint8_t* seg = mp + pos + lane * SEG;
+    uint64_t done;  // message bytes [.., done) are covered by acc
+    if (left >= PAGE) {
+      acc = rocp2p_crc_apply(s.shift[5], rocp2p_crc_apply(s.shift[5], acc)) ^
+            crc_page(seg, lane, s);
+      done = pos + PAGE;
+    } else {
+      const uint32_t valid = (uint32_t)left;  // 1..4095
+      const uint32_t beg = lane * SEG;
+      const uint32_t nb = valid > beg ? min(valid - beg, SEG) : 0u;
+      uint32_t w[16];
+      crc_load_partial(seg, nb, w);
+      uint32_t x = 0;
+      if (nb)
+        x = rocp2p_crc_mulmod(
+            rocp2p_crc_xpow8(valid - (beg + nb), c_crc.xpow8),
+            crc_bytes64(s.slice, w, nb));
+      for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
+      if (lane == 0) atomicXor(&out[cur.m], x);
+      done = pos;  // acc (if any) still has `valid` bytes after it
+    }
+    const bool msg_end = cur.ci + 1 == cur.cpm;
+    if (msg_end || c + 1 == c1) {
+      if (acc) {  // a zero CRC contributes nothing wherever it sits
+        const uint64_t r = cur.len - done;
+        uint32_t f = acc;
+        if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
+        if (msg_end) {
+          if (lane == 0) atomicXor(&out[cur.m], f);
+        } else {
+          pend_f = f;
+          pend_m = (uint32_t)cur.m;
+        }
+      }
+      acc = 0;
+    }
+    if (c + 1 < c1 && rocp2p_vl_next(&cur, cstart, lens))
+      mp = base + offs[cur.m];
+  }
+
+  __syncthreads();  // the tables are dead: their first words hand off
+  vl_merge_pending(&s.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
+}
+
+// ---------------------------------------------------------------------
 // launchers
 
 static inline uint32_t stream_grid(uint64_t items, uint32_t per_block) {
@@ -925,4 +1227,124 @@ extern "C" hipError_t rocp2p_crc32_region(const void* buf, uint64_t nbytes,
   if ((uintptr_t)buf % 16) return hipErrorInvalidValue;
   return crc32_digest_launch(buf, nullptr, nbytes, 1, d_out, grid_cap,
                              stream);
+}
+
+// ---------------------------------------------------------------------
+// Variable-length launchers: the scan, then the main kernel, on one
+// stream with no host step in between.  The host knows only an upper
+// bound of the chunk total (n messages of at most max_msg_bytes; 0 =
+// unknown, take the cap): it sizes the grid and nothing else, the
+// kernels take the real total from d_cstart[n].
+
+static uint32_t vl_grid(uint32_t n, uint64_t max_msg_bytes, uint64_t waves,
+                        uint64_t cap) {
+  if (!cap) cap = 1;
+  if (!max_msg_bytes) return (uint32_t)cap;
+  uint64_t bound;
+  if (__builtin_mul_overflow(rocp2p_vl_chunks(max_msg_bytes), (uint64_t)n,
+                             &bound))
+    return (uint32_t)cap;
+  uint64_t blocks = bound / waves + (bound % waves != 0);
+  return (uint32_t)(blocks > cap ? cap : blocks);  // >= 1: n, max > 0
+}
+
+static hipError_t vl_scan_launch(const uint64_t* d_lens, uint32_t n,
+                                 uint64_t* d_cstart, hipStream_t stream) {
+  hipLaunchKernelGGL(k_vl_scan, dim3(1), dim3(VL_SCAN_THREADS), 0, stream,
+                     d_lens, n, d_cstart);
+  return hipGetLastError();
+}
+
+template <bool GATHER>
+static hipError_t msg_engine_v_launch(void* region, const uint64_t* d_offs,
+                                      const uint64_t* d_addrs,
+                                      const uint64_t* d_lens, uint32_t n,
+                                      uint64_t max_msg_bytes,
+                                      uint64_t* d_cstart, uint32_t* d_out,
+                                      uint32_t grid_cap, hipStream_t stream) {
+  if (!d_cstart || (uintptr_t)region % 16) return hipErrorInvalidValue;
+  if (!n) return hipSuccess;
+  hipError_t e;
+  uint64_t cap = gather_grid_cap();
+  if (d_out) {
+    e = crc_tables_ready();
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+  }
+  // The fused form keeps k_msg_engine_crc's 128 workgroups.  The plain
+  // gather has the same four 16-byte PCIe reads per lane in flight and,
+  // measured on MI355X, the same optimum (4 KiB and 1 MiB messages:
+  // 53.0 GB/s at 512 workgroups, 53.5 at 256, 56.1-56.7 at 128 and 64);
+  // only batches known to hold sub-chunk messages, whose waves have few
+  // lanes busy, do better with the full cap (64 B: 19.6 GB/s at 128,
+  // 22.4 at 512).  The plain scatter does not care from 4 KiB up and
+  // wants the full cap at 64 B (21.5 at 128, 26.1 at 512).
+  const bool small = max_msg_bytes && max_msg_bytes < PAGE;
+  if ((d_out || (GATHER && !small)) && cap > ICRC_GRID) cap = ICRC_GRID;
+  if (grid_cap && grid_cap < cap) cap = grid_cap;
+  e = vl_scan_launch(d_lens, n, d_cstart, stream);
+  if (e != hipSuccess) return e;
+  const uint32_t grid = vl_grid(n, max_msg_bytes, ICRC_WAVES, cap);
+  if (d_out)
+    hipLaunchKernelGGL((k_msg_engine_v<GATHER, true>), dim3(grid),
+                       dim3(WAVE * ICRC_WAVES), 0, stream, (uint8_t*)region,
+                       d_offs, d_addrs, d_lens, (const uint64_t*)d_cstart, n,
+                       d_out);
+  else
+    hipLaunchKernelGGL((k_msg_engine_v<GATHER, false>), dim3(grid),
+                       dim3(WAVE * ICRC_WAVES), 0, stream, (uint8_t*)region,
+                       d_offs, d_addrs, d_lens, (const uint64_t*)d_cstart, n,
+                       d_out);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rocp2p_gather_v(void* dst_base,
+                                      const uint64_t* d_dst_offs,
+                                      const uint64_t* d_src_addrs,
+                                      const uint64_t* d_lens, uint32_t n,
+                                      uint64_t max_msg_bytes,
+                                      uint64_t* d_cstart, uint32_t* d_out,
+                                      uint32_t grid_cap, hipStream_t stream) {
+  return msg_engine_v_launch<true>(dst_base, d_dst_offs, d_src_addrs, d_lens,
+                                   n, max_msg_bytes, d_cstart, d_out,
+                                   grid_cap, stream);
+}
+
+extern "C" hipError_t rocp2p_scatter_v(const void* src_base,
+                                       const uint64_t* d_src_offs,
+                                       const uint64_t* d_dst_addrs,
+                                       const uint64_t* d_lens, uint32_t n,
+                                       uint64_t max_msg_bytes,
+                                       uint64_t* d_cstart, uint32_t* d_out,
+                                       uint32_t grid_cap,
+                                       hipStream_t stream) {
+  // the scatter instantiations only read the region
+  return msg_engine_v_launch<false>(const_cast<void*>(src_base), d_src_offs,
+                                    d_dst_addrs, d_lens, n, max_msg_bytes,
+                                    d_cstart, d_out, grid_cap, stream);
+}
+
+extern "C" hipError_t rocp2p_crc32_msgs_v(const void* base,
+                                          const uint64_t* d_offs,
+                                          const uint64_t* d_lens, uint32_t n,
+                                          uint64_t max_msg_bytes,
+                                          uint64_t* d_cstart, uint32_t* d_out,
+                                          uint32_t grid_cap,
+                                          hipStream_t stream) {
+  if (!d_cstart || (uintptr_t)base % 16) return hipErrorInvalidValue;
+  if (!n) return hipSuccess;
+  hipError_t e = crc_tables_ready();
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+  if (e != hipSuccess) return e;
+  e = vl_scan_launch(d_lens, n, d_cstart, stream);
+  if (e != hipSuccess) return e;
+  const uint32_t grid =
+      vl_grid(n, max_msg_bytes, CRC_DIGEST_WAVES, grid_cap ? grid_cap : 256);
+  hipLaunchKernelGGL(k_crc32_msgs_v, dim3(grid),
+                     dim3(WAVE * CRC_DIGEST_WAVES), 0, stream,
+                     (const uint8_t*)base, d_offs, d_lens,
+                     (const uint64_t*)d_cstart, n, d_out);
+  return hipGetLastError();
 }

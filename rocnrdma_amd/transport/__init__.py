@@ -49,6 +49,10 @@ def get_transport(name: str, **kw) -> Transport:
             raise NotImplementedError(
                 "verbs transport does not implement icrc=True (an HCA "
                 "checks its own ICRC)")
+        if kw.get("var_len"):
+            raise NotImplementedError(
+                "verbs transport does not implement var_len=True (the "
+                "native harness posts fixed-size work requests)")
         from .verbs import VerbsTransport
 
         return VerbsTransport(**kw)

@@ -21,6 +21,15 @@ afterwards is digested while it is moved and compared with its stamp,
 and `icrc_stats()` reads the running {"checked", "bad"} counters.  The
 inline digest is of the bytes as the engine loaded them; what landed in
 the receiving memory is still proven by integrity_check/digest_check.
+
+`var_len=True` (opt-in, backends that support it) lets every post carry
+its own byte count, as every verbs work request does: `msg_bytes`
+becomes the slot size, message i still goes to region offset
+(i % msgs_per_region) * msg_bytes and staging slot i % inflight, and
+`post(i, nbytes)` / `post_many(start, n, nbytes)` move only the first
+nbytes (0 <= nbytes <= msg_bytes, a multiple of 16) of the slot and of
+the region message; the rest of both is untouched.
+`digest_check(payload, lens)` audits such traffic, slack included.
 """
 from __future__ import annotations
 
@@ -30,13 +39,17 @@ import abc
 class Transport(abc.ABC):
     name = "base"
     supports_icrc = False
+    supports_var_len = False
 
     def __init__(self, msg_bytes: int, region_bytes: int,
                  inflight: int | None = 8, direction: str = "write",
-                 icrc: bool = False, **_):
+                 icrc: bool = False, var_len: bool = False, **_):
         if icrc and not self.supports_icrc:
             raise NotImplementedError(
                 f"{self.name} transport does not implement icrc=True")
+        if var_len and not self.supports_var_len:
+            raise NotImplementedError(
+                f"{self.name} transport does not implement var_len=True")
         if region_bytes % msg_bytes:
             raise ValueError("region must be a multiple of msg size")
         if direction not in ("write", "read"):
@@ -48,21 +61,69 @@ class Transport(abc.ABC):
         self.inflight = max(1, min(inflight, region_bytes // msg_bytes))
         self.direction = direction
         self.icrc = bool(icrc)
+        self.var_len = bool(var_len)
 
     # -- data plane ----------------------------------------------------
     @abc.abstractmethod
-    def post(self, i: int) -> None:
-        """Enqueue message i (non-blocking where the backend allows)."""
+    def post(self, i: int, nbytes: int | None = None) -> None:
+        """Enqueue message i (non-blocking where the backend allows).
+        nbytes (var_len=True only): this message's byte count, None =
+        msg_bytes."""
 
     @abc.abstractmethod
     def flush(self) -> None:
         """Complete every outstanding message."""
 
-    def post_many(self, start: int, n: int) -> None:
+    def post_many(self, start: int, n: int, nbytes=None) -> None:
         """Enqueue messages start..start+n-1 (backends may vectorize the
-        WQE writes; semantics identical to n post() calls)."""
-        for i in range(start, start + n):
-            self.post(i)
+        WQE writes; semantics identical to n post() calls).  nbytes
+        (var_len=True only): one byte count for all, or an integer array
+        of n."""
+        if nbytes is None:
+            for i in range(start, start + n):
+                self.post(i)
+            return
+        lens = self._lens(nbytes, n)
+        for k in range(n):
+            self.post(start + k, int(lens[k]))
+
+    def _lens(self, nbytes, n: int):
+        """nbytes of n posts as a validated int64 array (None = full
+        slots): 0 <= nbytes <= msg_bytes, multiples of 16."""
+        import numpy as np
+
+        if not self.var_len:
+            raise ValueError(
+                f"nbytes needs a transport opened with var_len=True "
+                f"(this {self.name} transport moves msg_bytes per message)")
+        if nbytes is None:
+            return np.full(n, self.msg_bytes, dtype=np.int64)
+        arr = np.asarray(nbytes)
+        if arr.dtype.kind not in "iu":
+            raise ValueError("nbytes must be integers")
+        if arr.ndim == 0:
+            arr = np.full(n, arr)
+        elif arr.shape != (n,):
+            raise ValueError(f"nbytes must be a scalar or {n} entries")
+        if arr.dtype.kind == "u" and arr.size and int(arr.max()) > self.msg_bytes:
+            raise ValueError("nbytes above msg_bytes")
+        arr = arr.astype(np.int64)
+        if ((arr < 0) | (arr > self.msg_bytes) | (arr % 16 != 0)).any():
+            raise ValueError(
+                f"nbytes must be multiples of 16 in [0, {self.msg_bytes}]")
+        return arr
+
+    def _len1(self, nbytes) -> int:
+        """_lens for one post, without numpy."""
+        if nbytes is None:
+            return self.msg_bytes
+        if not self.var_len:
+            self._lens(nbytes, 1)  # raises
+        ln = int(nbytes)
+        if ln != nbytes or not 0 <= ln <= self.msg_bytes or ln % 16:
+            raise ValueError(
+                f"nbytes must be a multiple of 16 in [0, {self.msg_bytes}]")
+        return ln
 
     # -- integrity plane (never timed) ---------------------------------
     @abc.abstractmethod
@@ -70,12 +131,19 @@ class Transport(abc.ABC):
         """Move the whole region with pattern payloads; return mismatching
         8-byte words at the receiver (0 = intact)."""
 
-    def digest_check(self, payload) -> int:
+    def digest_check(self, payload, lens=None) -> int:
         """Payload-agnostic check: move the whole region carrying
         `payload` (any uint8 array of region_bytes, arbitrary content) in
         the same bursts as integrity_check; return the number of MESSAGES
         whose receiver CRC32 digest differs from the sender's (0 =
-        intact).  Optional: backends without it raise."""
+        intact).  Optional: backends without it raise.
+
+        lens (var_len=True only): message j carries payload[j * msg_bytes
+        : j * msg_bytes + lens[j]]; None = full slots.  The receiving
+        side is set to a known byte first and every slack range
+        [j * msg_bytes + lens[j], (j + 1) * msg_bytes) must still hold
+        it afterwards: a message is bad if its digest differs or its
+        slack changed."""
         raise NotImplementedError(
             f"{self.name} transport does not implement digest_check")
 
@@ -86,6 +154,7 @@ class Transport(abc.ABC):
         posted from here on are compared with it while they move; call
         it again after changing the sender's content.  integrity_check
         and digest_check rewrite the sender and drop the stamp."""
+        self._no_stamp_with_var_len()
         raise NotImplementedError(
             f"{self.name} transport was not opened with icrc=True")
 
@@ -94,6 +163,14 @@ class Transport(abc.ABC):
         "bad": how many of them differed}."""
         raise NotImplementedError(
             f"{self.name} transport was not opened with icrc=True")
+
+    def _no_stamp_with_var_len(self) -> None:
+        if self.var_len:
+            raise NotImplementedError(
+                "stamp() is not available with var_len=True: a stamp is "
+                "one digest per slot (or region message), taken before "
+                "the posts, and cannot know the length a later post will "
+                "carry; icrc=True still serves digest_check(payload, lens)")
 
     def _payload_bytes(self, payload):
         """payload as a flat contiguous uint8 numpy array of region_bytes."""

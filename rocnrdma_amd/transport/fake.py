@@ -14,6 +14,8 @@ from .base import Transport
 class FakeTransport(Transport):
     name = "fake"
     supports_icrc = True  # zlib on the host: the sdma logic, CPU tier
+    supports_var_len = True
+    KNOWN = 0x5A  # what digest_check(payload, lens) leaves in the slack
 
     def __init__(self, msg_bytes: int, region_bytes: int, **kw):
         super().__init__(msg_bytes, region_bytes, **kw)
@@ -24,10 +26,11 @@ class FakeTransport(Transport):
             self._checked = self._bad = 0
             self._inline = None  # digests of a running digest_check
 
-    def post(self, i: int) -> None:
-        slot = self.staging[i % self.inflight]
+    def post(self, i: int, nbytes: int | None = None) -> None:
+        ln = self._len1(nbytes)
+        slot = self.staging[i % self.inflight][:ln]
         off = (i % self.msgs_per_region) * self.msg_bytes
-        dst = self.region[off : off + self.msg_bytes]
+        dst = self.region[off : off + ln]
         if self.icrc:
             self._digest(i, slot if self.direction == "write" else dst)
         if self.direction == "write":
@@ -51,7 +54,7 @@ class FakeTransport(Transport):
         pass
 
     def stamp(self) -> None:
-        if not self.icrc:
+        if not self.icrc or self.var_len:
             return super().stamp()
         if self.direction == "write":
             self._expected = np.array(
@@ -92,9 +95,11 @@ class FakeTransport(Transport):
                     != ref[off : off + self.msg_bytes].view(np.uint64)))
         return bad
 
-    def digest_check(self, payload) -> int:
+    def digest_check(self, payload, lens=None) -> int:
         pay = self._payload_bytes(payload)
         n, msg = self.msgs_per_region, self.msg_bytes
+        if self.var_len or lens is not None:
+            return self._digest_check_var(pay, self._lens(lens, n))
         if self.icrc:
             # the region-side digests come from the inline ICRC of the
             # transfer itself, not from a second pass over the region
@@ -126,6 +131,54 @@ class FakeTransport(Transport):
                 want = self._inline[i] if self.icrc else int(sent[i])
                 bad += int(got != want)
             return bad
+        finally:
+            if self.icrc:
+                self._inline = None
+
+    def _digest_check_var(self, pay, lens) -> int:
+        """digest_check for per-message lengths: digests of the first
+        lens[j] bytes, and the receiver's slack must keep KNOWN."""
+        n, msg = self.msgs_per_region, self.msg_bytes
+        write = self.direction == "write"
+        if self.icrc:
+            self._expected = None
+            self._inline = []
+        try:
+            bad = np.zeros(n, dtype=bool)
+            if write:
+                self.region[:] = self.KNOWN
+                sent = np.empty(n, dtype=np.uint32)
+                for i in range(n):
+                    slot = self.staging[i % self.inflight]
+                    slot[:] = pay[i * msg : (i + 1) * msg]
+                    sent[i] = zlib.crc32(slot[: lens[i]].tobytes())
+                    self.post(i, int(lens[i]))
+                self.flush()
+                offs = np.arange(n, dtype=np.int64) * msg
+                if self.icrc:
+                    got = np.array(self._inline, np.uint32)
+                else:
+                    got = pattern.crc32_messages_v_reference(
+                        self.region, offs, lens)
+                bad |= got != sent
+                for i in range(n):
+                    slack = self.region[i * msg + lens[i] : (i + 1) * msg]
+                    bad[i] |= bool((slack != self.KNOWN).any())
+                return int(bad.sum())
+            # read: load the region, pull every message into a slot that
+            # holds KNOWN, digest and inspect the slot
+            self.region[:] = pay
+            for i in range(n):
+                slot = self.staging[i % self.inflight]
+                slot[:] = self.KNOWN
+                self.post(i, int(lens[i]))
+                self.flush()
+                ln = int(lens[i])
+                got = zlib.crc32(slot[:ln].tobytes())
+                want = (self._inline[i] if self.icrc else
+                        zlib.crc32(pay[i * msg : i * msg + ln].tobytes()))
+                bad[i] = got != want or bool((slot[ln:] != self.KNOWN).any())
+            return int(bad.sum())
         finally:
             if self.icrc:
                 self._inline = None

@@ -25,6 +25,10 @@ icrc=True (kernel engine only) swaps in the fused engine
 digests every message, and the digests are compared with the stamped
 expectations on the same stream — each WQE carries a third word for
 that — into two device counters.  No host readback, no extra sync.
+
+var_len=True (kernel engine only) gives every WQE a length word and
+retires the ring with ops.gather_v_/scatter_v_ (crc=icrc): msg_bytes is
+the slot size, each message moves only the bytes its post asked for.
 """
 from __future__ import annotations
 
@@ -36,10 +40,18 @@ from .base import Transport
 _KERNEL_THRESHOLD = 8 << 20
 _STAGING_TARGET = 64 << 20  # pinned staging budget for small messages
 
+# Rows of the WQE ring.  The optional rows follow in this order: the
+# message's byte count (var_len), then what the inline digest is compared
+# with (icrc): the expected CRC32 of the slot (write), or the region
+# message whose stamp stays on the device (read).
+ROW_OFF, ROW_ADDR = 0, 1  # region offset, staging address
+_KNOWN = 0x5A  # what digest_check(payload, lens) leaves in the slack
+
 
 class SdmaTransport(Transport):
     name = "sdma"
     supports_icrc = True
+    supports_var_len = True
 
     def __init__(self, msg_bytes: int, region_bytes: int, device=None,
                  num_streams: int = 2, engine: str = "auto",
@@ -55,6 +67,11 @@ class SdmaTransport(Transport):
                 "(explicit, or picked by auto for messages of 8 MiB and "
                 "up) moves data with hipMemcpyAsync, where no kernel "
                 "sees the bytes to digest them")
+        if kw.get("var_len") and engine != "kernel":
+            raise ValueError(
+                "var_len=True needs the kernel engine: only its WQEs "
+                "carry a length; the stream engine (explicit, or picked "
+                "by auto for slots of 8 MiB and up) copies whole slots")
         if inflight in (None, 0):
             if engine == "kernel":
                 inflight = max(8, min(region_bytes // msg_bytes,
@@ -82,11 +99,13 @@ class SdmaTransport(Transport):
             self._slot_addr = [base + i * msg_bytes
                                for i in range(self.inflight)]
             self._slot_addr_np = np.array(self._slot_addr, dtype=np.int64)
-            # WQE ring: [0] = region offset, [1] = staging address; with
-            # icrc [2] = what the digest is compared with: the expected
-            # CRC32 of the slot (write), or the region message whose
-            # stamp stays on the device (read)
-            rows = 3 if self.icrc else 2
+            # WQE ring: ROW_OFF, ROW_ADDR, then the optional rows
+            rows = 2
+            self._row_len = self._row_exp = None
+            if self.var_len:
+                self._row_len, rows = rows, rows + 1
+            if self.icrc:
+                self._row_exp, rows = rows, rows + 1
             self._desc_pin = torch.empty((rows, self.inflight),
                                          dtype=torch.int64, pin_memory=True)
             self._desc_np = self._desc_pin.numpy()
@@ -106,17 +125,21 @@ class SdmaTransport(Transport):
             torch.cuda.synchronize(self.device)
 
     # -- data plane ----------------------------------------------------
-    def post(self, i: int) -> None:
+    def post(self, i: int, nbytes: int | None = None) -> None:
+        if nbytes is not None or self.var_len:
+            nbytes = self._len1(nbytes)
         off = (i % self.msgs_per_region) * self.msg_bytes
         slot = i % self.inflight
         if self.engine == "kernel":
             if self._pending >= self.inflight:
                 self.flush()
             k = self._pending
-            self._desc_np[0, k] = off
-            self._desc_np[1, k] = self._slot_addr[slot]
+            self._desc_np[ROW_OFF, k] = off
+            self._desc_np[ROW_ADDR, k] = self._slot_addr[slot]
+            if self.var_len:
+                self._desc_np[self._row_len, k] = nbytes
             if self.icrc and self._stamped:
-                self._desc_np[2, k] = (
+                self._desc_np[self._row_exp, k] = (
                     self._exp_slot_np[slot] if self.direction == "write"
                     else i % self.msgs_per_region)
             self._pending = k + 1
@@ -129,14 +152,17 @@ class SdmaTransport(Transport):
             else:
                 self.staging[slot].copy_(dst, non_blocking=True)
 
-    def post_many(self, start: int, n: int) -> None:
+    def post_many(self, start: int, n: int, nbytes=None) -> None:
         """Vectorized WQE writes (numpy) — the posting loop itself must
         not bound small-message rates (a verbs app posts in C; measured:
         scalar python post() capped 4 KiB at ~10 GB/s)."""
         if self.engine != "kernel":
-            return super().post_many(start, n)
+            return super().post_many(start, n, nbytes)
         import numpy as np
 
+        lens = None
+        if nbytes is not None or self.var_len:
+            lens = self._lens(nbytes, n)  # one vectorized check
         done = 0
         while done < n:
             if self._pending >= self.inflight:
@@ -145,12 +171,15 @@ class SdmaTransport(Transport):
             take = min(n - done, self.inflight - k)
             idx = np.arange(start + done, start + done + take,
                             dtype=np.int64)
-            self._desc_np[0, k:k + take] = \
+            self._desc_np[ROW_OFF, k:k + take] = \
                 (idx % self.msgs_per_region) * self.msg_bytes
-            self._desc_np[1, k:k + take] = \
+            self._desc_np[ROW_ADDR, k:k + take] = \
                 self._slot_addr_np[idx % self.inflight]
+            if lens is not None:
+                self._desc_np[self._row_len, k:k + take] = \
+                    lens[done:done + take]
             if self.icrc and self._stamped:
-                self._desc_np[2, k:k + take] = (
+                self._desc_np[self._row_exp, k:k + take] = (
                     self._exp_slot_np[idx % self.inflight]
                     if self.direction == "write"
                     else idx % self.msgs_per_region)
@@ -168,14 +197,18 @@ class SdmaTransport(Transport):
                 with torch.cuda.stream(stream):
                     self._desc_dev[:, :n].copy_(self._desc_pin[:, :n],
                                                 non_blocking=True)
-                    if self.icrc:
+                    if self.var_len:
+                        self._flush_var_len(n)
+                    elif self.icrc:
                         self._flush_icrc(n)
                     elif self.direction == "write":
-                        ops.gather_(self.region, self._desc_dev[0, :n],
-                                    self._desc_dev[1, :n], self.msg_bytes)
+                        ops.gather_(self.region, self._desc_dev[ROW_OFF, :n],
+                                    self._desc_dev[ROW_ADDR, :n],
+                                    self.msg_bytes)
                     else:
-                        ops.scatter_(self.region, self._desc_dev[0, :n],
-                                     self._desc_dev[1, :n], self.msg_bytes)
+                        ops.scatter_(self.region, self._desc_dev[ROW_OFF, :n],
+                                     self._desc_dev[ROW_ADDR, :n],
+                                     self.msg_bytes)
             self.streams[0].synchronize()
             return
         for s in self.streams:
@@ -187,18 +220,32 @@ class SdmaTransport(Transport):
 
         engine = (ops.gather_crc_ if self.direction == "write"
                   else ops.scatter_crc_)
-        dig = engine(self.region, self._desc_dev[0, :n],
-                     self._desc_dev[1, :n], self.msg_bytes)
+        dig = engine(self.region, self._desc_dev[ROW_OFF, :n],
+                     self._desc_dev[ROW_ADDR, :n], self.msg_bytes)
         self._last_digests = dig
         if not self._stamped:
             return
-        field = self._desc_dev[2, :n]
+        field = self._desc_dev[self._row_exp, :n]
         exp = field if self.direction == "write" else self._exp_dev[field]
         self._icrc_dev[0].add_(n)
         self._icrc_dev[1].add_((dig != exp).sum())
 
+    def _flush_var_len(self, n: int) -> None:
+        """One variable-length engine launch for the ring, on the current
+        (flush) stream; with icrc the digests of the batch are kept."""
+        from .. import ops
+
+        engine = (ops.gather_v_ if self.direction == "write"
+                  else ops.scatter_v_)
+        dig = engine(self.region, self._desc_dev[ROW_OFF, :n],
+                     self._desc_dev[ROW_ADDR, :n],
+                     self._desc_dev[self._row_len, :n],
+                     max_msg_bytes=self.msg_bytes, crc=self.icrc)
+        if self.icrc:
+            self._last_digests = dig
+
     def stamp(self) -> None:
-        if not self.icrc:
+        if not self.icrc or self.var_len:
             return super().stamp()
         import zlib
 
@@ -264,7 +311,7 @@ class SdmaTransport(Transport):
             i += burst
         return bad
 
-    def digest_check(self, payload) -> int:
+    def digest_check(self, payload, lens=None) -> int:
         """Per-message CRC32 of arbitrary content, sender vs receiver.
         The HBM side is digested by one crc32_messages launch, so only
         4 bytes per message ever cross back — no payload readback."""
@@ -277,6 +324,8 @@ class SdmaTransport(Transport):
         pay = self._payload_bytes(payload)
         pay_t = torch.from_numpy(pay)
         n, msg = self.msgs_per_region, self.msg_bytes
+        if self.var_len or lens is not None:
+            return self._digest_check_var_len(pay_t, self._lens(lens, n))
         if self.icrc:
             return self._digest_check_icrc(pay_t)
         if self.direction == "write":
@@ -346,6 +395,70 @@ class SdmaTransport(Transport):
             i += burst
         got = torch.cat(inline).cpu().numpy().view(np.uint32)
         return int(np.count_nonzero(got != host))
+
+    def _digest_check_var_len(self, pay_t, lens) -> int:
+        """digest_check for per-message lengths.  HBM-side digests: the
+        fused engine's (icrc) or one crc32_messages_v launch; host side:
+        zlib.  The receiver starts as _KNOWN everywhere and its slack
+        ranges must still hold it: in HBM a second crc32_messages_v over
+        the slack ranges against the digest of that many _KNOWN bytes,
+        on the host numpy."""
+        import zlib
+
+        import numpy as np
+
+        from .. import ops
+
+        n, msg = self.msgs_per_region, self.msg_bytes
+        write = self.direction == "write"
+        if self.icrc:
+            self._stamped = False
+        offs = np.arange(n, dtype=np.int64) * msg
+        d_offs = torch.from_numpy(offs).to(self.device)
+        d_lens = torch.from_numpy(lens).to(self.device)
+        if write:
+            self.region.fill_(_KNOWN)
+        else:
+            self.region.copy_(pay_t)
+        torch.cuda.synchronize(self.device)
+        host = np.empty(n, dtype=np.uint32)
+        bad = np.zeros(n, dtype=bool)
+        inline = []
+        i = 0
+        while i < n:
+            burst = min(self.inflight, n - i)
+            if not write:
+                self.staging_flat[:burst * msg].fill_(_KNOWN)
+            else:
+                for j in range(i, i + burst):
+                    slot = self.staging[j % self.inflight]
+                    slot.copy_(pay_t[j * msg:(j + 1) * msg])
+                    host[j] = zlib.crc32(slot.numpy()[:lens[j]])
+            self.post_many(i, burst, lens[i:i + burst])
+            self.flush()  # slots reused next burst: must complete
+            if self.icrc:
+                inline.append(self._last_digests)
+            if not write:
+                for j in range(i, i + burst):
+                    slot = self.staging[j % self.inflight].numpy()
+                    host[j] = zlib.crc32(slot[:lens[j]])
+                    bad[j] = bool((slot[lens[j]:] != _KNOWN).any())
+            i += burst
+        if self.icrc:
+            hbm = torch.cat(inline)
+        else:
+            hbm = ops.crc32_messages_v(self.region, d_offs, d_lens,
+                                       max_msg_bytes=msg)
+        if write:
+            slack = ops.crc32_messages_v(self.region, d_offs + d_lens,
+                                         msg - d_lens, max_msg_bytes=msg)
+            known = {int(k): zlib.crc32(bytes([_KNOWN]) * int(k))
+                     for k in np.unique(msg - lens)}
+            want = np.array([known[int(msg - ln)] for ln in lens],
+                            dtype=np.uint32)
+            bad |= slack.cpu().numpy().view(np.uint32) != want
+        bad |= hbm.cpu().numpy().view(np.uint32) != host
+        return int(bad.sum())
 
     def close(self) -> None:
         self.flush()

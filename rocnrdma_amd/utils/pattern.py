@@ -104,3 +104,17 @@ def crc32_messages_reference(data: bytes | np.ndarray, msg_bytes: int,
         assert 0 <= o and o + msg_bytes <= len(buf)
         out.append(zlib.crc32(buf[o : o + msg_bytes]))
     return np.array(out, dtype=np.uint32)
+
+
+def crc32_messages_v_reference(data: bytes | np.ndarray, offs,
+                               lens) -> np.ndarray:
+    """zlib.crc32 of data[offs[m] : offs[m] + lens[m]] for every m, as
+    uint32 array (a zero-length message digests to 0)."""
+    buf = np.asarray(data, dtype=np.uint8).tobytes()
+    assert len(offs) == len(lens)
+    out = []
+    for o, ln in zip(offs, lens):
+        o, ln = int(o), int(ln)
+        assert 0 <= o and 0 <= ln and o + ln <= len(buf)
+        out.append(zlib.crc32(buf[o : o + ln]))
+    return np.array(out, dtype=np.uint32)
