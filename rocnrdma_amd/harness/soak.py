@@ -5,6 +5,7 @@ deploy candidate; the GPU test tier runs a short bounded pass).
 
 CLI: python -m rocnrdma_amd.harness.soak [--secs 30] [--transport auto]
                                          [--audit pattern|crc] [--mixed]
+                                         [--bytes]
 Exit nonzero on any integrity failure.
 """
 from __future__ import annotations
@@ -16,21 +17,23 @@ import time
 SIZES = [4 << 10, 16 << 10, 64 << 10, 256 << 10, 1 << 20, 4 << 20]
 
 
-def mixed_lens(rng: random.Random, n: int, msg: int):
+def mixed_lens(rng: random.Random, n: int, msg: int, unit: int = 16):
     """n seeded message lengths for a slot of msg bytes: multiples of 16
     in [0, msg], with mass on 0, 16, msg and just around the 4096-byte
-    chunk boundaries, where the engine changes path."""
+    chunk boundaries, where the engine changes path.  unit=1 (--bytes)
+    draws from all byte counts instead, with the mass on 0, 1, msg and
+    one byte either side of the boundaries."""
     import numpy as np
 
     g = np.random.default_rng(rng.getrandbits(32))
-    lens = g.integers(0, msg // 16 + 1, n, dtype=np.int64) * 16
+    lens = g.integers(0, msg // unit + 1, n, dtype=np.int64) * unit
     kind = g.random(n)
     lens[kind < 0.10] = 0
-    lens[(kind >= 0.10) & (kind < 0.20)] = 16
+    lens[(kind >= 0.10) & (kind < 0.20)] = unit
     lens[(kind >= 0.20) & (kind < 0.35)] = msg
     edge = (kind >= 0.35) & (kind < 0.55)
     near = (g.integers(1, max(msg // 4096, 1) + 1, n, dtype=np.int64) * 4096
-            + g.integers(-1, 2, n, dtype=np.int64) * 16)
+            + g.integers(-1, 2, n, dtype=np.int64) * unit)
     lens[edge] = np.clip(near, 0, msg)[edge]
     return lens
 
@@ -38,7 +41,8 @@ def mixed_lens(rng: random.Random, n: int, msg: int):
 def run_soak(transport: str = "auto", secs: float = 10.0,
              region_bytes: int = 256 << 20, seed: int = 1234,
              device=None, metrics=None, audit: str = "pattern",
-             icrc: bool = False, mixed: bool = False) -> dict:
+             icrc: bool = False, mixed: bool = False,
+             byte_granular: bool = False) -> dict:
     """audit="pattern": splitmix64 pattern + integrity_check (default).
     audit="crc": a seeded random payload per cycle through digest_check
     (per-message CRC32, content-independent).
@@ -50,12 +54,17 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
     (mixed_lens) and audits with digest_check(payload, lens), slack
     included; msgs and bytes count what was actually moved.  A stamp
     cannot serve variable lengths, so with icrc=True the inline digests
-    are used by the audit only."""
+    are used by the audit only.
+    byte_granular=True (needs mixed): the transport is opened with
+    byte_granular=True and a seeded region_skew / staging_skew per cycle,
+    and the lengths are drawn from all byte counts that fit."""
     from rocnrdma_amd.harness.sweep import pattern_sender
     from rocnrdma_amd.transport import get_transport
 
     if audit not in ("pattern", "crc"):
         raise ValueError(f"audit must be 'pattern' or 'crc', not {audit!r}")
+    if byte_granular and not mixed:
+        raise ValueError("byte_granular=True needs mixed=True")
 
     if metrics is None:
         from rocnrdma_amd.utils.metrics import TransferMetrics
@@ -75,6 +84,9 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
         msg = rng.choice(SIZES)
         direction = rng.choice(["write", "read"])
         region = max(region_bytes // msg, 1) * msg
+        if byte_granular:
+            extra.update(byte_granular=True, region_skew=rng.randrange(16),
+                         staging_skew=rng.randrange(16))
         tp = get_transport(transport, msg_bytes=msg, region_bytes=region,
                            direction=direction, device=device, **extra)
         try:
@@ -136,17 +148,18 @@ def _mixed_cycle(tp, rng: random.Random, region: int):
     moved, messages moved, bad messages of the audit)."""
     import numpy as np
 
+    unit = 1 if tp.byte_granular else 16
     moved = posted = 0
     for _ in range(rng.randint(1, 4)):
         burst = rng.randint(1, max(2, tp.inflight))
-        lens = mixed_lens(rng, burst, tp.msg_bytes)
+        lens = mixed_lens(rng, burst, tp.max_nbytes, unit)
         tp.post_many(posted, burst, lens)
         posted += burst
         moved += int(lens.sum())
         tp.flush()
     payload = np.random.default_rng(rng.getrandbits(32)).integers(
         0, 256, region, dtype=np.uint8)
-    lens = mixed_lens(rng, tp.msgs_per_region, tp.msg_bytes)
+    lens = mixed_lens(rng, tp.msgs_per_region, tp.max_nbytes, unit)
     bad = tp.digest_check(payload, lens)
     return (moved + int(lens.sum()), posted + tp.msgs_per_region, bad)
 
@@ -168,6 +181,10 @@ def main():
                     help="variable-length traffic: var_len transport, "
                          "seeded random lengths per message, audited "
                          "with digest_check(payload, lens)")
+    ap.add_argument("--bytes", action="store_true", dest="byte_granular",
+                    help="with --mixed: byte-granular traffic, lengths "
+                         "from all byte counts (not multiples of 16) at a "
+                         "random skew per side")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="expose Prometheus metrics on this port")
     args = ap.parse_args()
@@ -176,7 +193,8 @@ def main():
     metrics = TransferMetrics(port=args.metrics_port or None)
     stats = run_soak(args.transport, args.secs, args.region_bytes,
                      args.seed, metrics=metrics, audit=args.audit,
-                     icrc=args.icrc, mixed=args.mixed)
+                     icrc=args.icrc, mixed=args.mixed,
+                     byte_granular=args.byte_granular)
     print(stats)
     raise SystemExit(1 if stats["failures"] else 0)
 

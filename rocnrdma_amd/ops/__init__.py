@@ -142,6 +142,44 @@ def crc32_messages_v(region: torch.Tensor, offs: torch.Tensor,
                                        grid_cap)
 
 
+def gather_bytes_(region: torch.Tensor, dst_offs: torch.Tensor,
+                  src_addrs: torch.Tensor, lens: torch.Tensor, *,
+                  max_msg_bytes: int = 0, crc: bool = False,
+                  grid_cap: int = 0) -> torch.Tensor | None:
+    """gather_v_ for byte-granular messages: lens[m] >= 0 is any byte
+    count, read from any byte address src_addrs[m] and written to any
+    byte offset dst_offs[m]; the relative misalignment (src - dst) mod 16
+    is arbitrary per message.  Only the region's base stays 16-byte
+    aligned.  No byte outside [start, start + len) of any message is
+    loaded or stored on either side (partial granules are written with
+    narrow stores of exactly their valid bytes, never read-modify-write,
+    so neighbours may share a granule); zero-length messages reach no
+    load, store or atomic and their digest is 0.  Keyword arguments and
+    result as for gather_v_; aligned multiples of 16 give what gather_v_
+    gives."""
+    return _require().gather_bytes_(region, dst_offs, src_addrs, lens,
+                                    max_msg_bytes, crc, grid_cap)
+
+
+def scatter_bytes_(region: torch.Tensor, src_offs: torch.Tensor,
+                   dst_addrs: torch.Tensor, lens: torch.Tensor, *,
+                   max_msg_bytes: int = 0, crc: bool = False,
+                   grid_cap: int = 0) -> torch.Tensor | None:
+    """scatter_v_ for byte-granular messages; see gather_bytes_."""
+    return _require().scatter_bytes_(region, src_offs, dst_addrs, lens,
+                                     max_msg_bytes, crc, grid_cap)
+
+
+def crc32_messages_bytes(region: torch.Tensor, offs: torch.Tensor,
+                         lens: torch.Tensor, *, max_msg_bytes: int = 0,
+                         grid_cap: int = 0) -> torch.Tensor:
+    """crc32_messages_v for offsets of any alignment: zlib's CRC32 of
+    region[offs[m] : offs[m] + lens[m]] for every m, no byte outside a
+    message loaded; int32 tensor[n] on GPU, no sync."""
+    return _require().crc32_messages_bytes(region, offs, lens,
+                                           max_msg_bytes, grid_cap)
+
+
 def dmabuf_fd(buf: torch.Tensor) -> int:
     """Export an HBM tensor as a dmabuf fd (ibv_reg_dmabuf_mr's GPU
     half). Caller must os.close() the fd."""

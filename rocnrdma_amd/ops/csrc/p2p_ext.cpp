@@ -281,6 +281,45 @@ torch::Tensor crc32_messages_v(torch::Tensor region, torch::Tensor offs,
   return out;
 }
 
+// The byte-granular forms: any length at any address (p2p_bytes.h).
+// Same host-visible checks as the _v forms — only the region base has
+// to be 16-byte aligned — and the same scratch and digest tensors.
+c10::optional<torch::Tensor> gather_bytes_(torch::Tensor region,
+                                           torch::Tensor dst_offs,
+                                           torch::Tensor src_addrs,
+                                           torch::Tensor lens,
+                                           int64_t max_msg_bytes, bool crc,
+                                           int64_t grid_cap) {
+  return msg_engine_v("gather_bytes_", rocp2p_gather_b, region, dst_offs,
+                      src_addrs, lens, max_msg_bytes, crc, grid_cap);
+}
+
+c10::optional<torch::Tensor> scatter_bytes_(torch::Tensor region,
+                                            torch::Tensor src_offs,
+                                            torch::Tensor dst_addrs,
+                                            torch::Tensor lens,
+                                            int64_t max_msg_bytes, bool crc,
+                                            int64_t grid_cap) {
+  return msg_engine_v("scatter_bytes_", rocp2p_scatter_b, region, src_offs,
+                      dst_addrs, lens, max_msg_bytes, crc, grid_cap);
+}
+
+torch::Tensor crc32_messages_bytes(torch::Tensor region, torch::Tensor offs,
+                                   torch::Tensor lens, int64_t max_msg_bytes,
+                                   int64_t grid_cap) {
+  OnDeviceOf dev(region, "crc32_messages_bytes");
+  VarLenArgs a("crc32_messages_bytes", region, offs, nullptr, lens,
+               max_msg_bytes, grid_cap);
+  auto out = torch::empty({a.n},
+                          torch::dtype(torch::kInt32).device(region.device()));
+  HIP_OK(rocp2p_crc32_msgs_b(
+      region.data_ptr(), (const uint64_t*)offs.data_ptr<int64_t>(),
+      (const uint64_t*)lens.data_ptr<int64_t>(), (uint32_t)a.n,
+      (uint64_t)max_msg_bytes, (uint64_t*)a.cstart.data_ptr<int64_t>(),
+      (uint32_t*)out.data_ptr<int32_t>(), (uint32_t)grid_cap, dev.stream));
+  return out;
+}
+
 void copy_(torch::Tensor dst, torch::Tensor src) {
   OnDeviceOf dev(dst, "copy_");
   check_buf(src, "copy_");
@@ -352,6 +391,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("crc") = false, py::arg("grid_cap") = 0);
   m.def("crc32_messages_v", &crc32_messages_v,
         "zlib CRC32 of each message base[offs[m], offs[m] + lens[m])",
+        py::arg("region"), py::arg("offs"), py::arg("lens"),
+        py::arg("max_msg_bytes") = 0, py::arg("grid_cap") = 0);
+  m.def("gather_bytes_", &gather_bytes_,
+        "gather_v_ for any byte length at any byte address",
+        py::arg("region"), py::arg("dst_offs"), py::arg("src_addrs"),
+        py::arg("lens"), py::arg("max_msg_bytes") = 0,
+        py::arg("crc") = false, py::arg("grid_cap") = 0);
+  m.def("scatter_bytes_", &scatter_bytes_,
+        "scatter_v_ for any byte length at any byte address",
+        py::arg("region"), py::arg("src_offs"), py::arg("dst_addrs"),
+        py::arg("lens"), py::arg("max_msg_bytes") = 0,
+        py::arg("crc") = false, py::arg("grid_cap") = 0);
+  m.def("crc32_messages_bytes", &crc32_messages_bytes,
+        "crc32_messages_v for offsets of any alignment",
         py::arg("region"), py::arg("offs"), py::arg("lens"),
         py::arg("max_msg_bytes") = 0, py::arg("grid_cap") = 0);
   m.def("dmabuf_fd", &dmabuf_fd,

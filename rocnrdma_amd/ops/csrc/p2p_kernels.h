@@ -131,4 +131,40 @@ hipError_t rocp2p_crc32_msgs_v(const void* base, const uint64_t* d_offs,
                                uint32_t* d_out, uint32_t grid_cap,
                                hipStream_t stream);
 
+// Byte-granular messages: the argument lists, errors and guarantees of
+// the _v calls above with "16" removed.  d_lens[m] >= 0 is any byte
+// count, read from any byte address and written to any byte address;
+// the relative misalignment (src - dst) mod 16 is arbitrary per message
+// (geometry: p2p_bytes.h).  Only the region base stays 16-byte aligned.
+// No byte outside [start, start + len) of any message is loaded or
+// stored on either side: full granules move as naturally aligned
+// 16-byte accesses, a partial first or last granule as naturally aligned
+// 1-, 2-, 4- and 8-byte accesses of exactly its valid bytes, never a
+// read-modify-write — neighbouring messages may share a granule.
+// Zero-length messages reach no load, store or atomic, their digest is
+// 0.  Results do not depend on max_msg_bytes, grid_cap or the grid.
+// Stream-ordered, allocate nothing, no host synchronise; d_cstart is
+// n + 1 words of scratch.  hipErrorInvalidValue: null d_cstart, base not
+// 16-byte aligned.  n == 0 is a no-op.  Aligned multiples of 16 give
+// what the _v calls give.
+hipError_t rocp2p_gather_b(void* dst_base, const uint64_t* d_dst_offs,
+                           const uint64_t* d_src_addrs,
+                           const uint64_t* d_lens, uint32_t n,
+                           uint64_t max_msg_bytes, uint64_t* d_cstart,
+                           uint32_t* d_out, uint32_t grid_cap,
+                           hipStream_t stream);
+hipError_t rocp2p_scatter_b(const void* src_base, const uint64_t* d_src_offs,
+                            const uint64_t* d_dst_addrs,
+                            const uint64_t* d_lens, uint32_t n,
+                            uint64_t max_msg_bytes, uint64_t* d_cstart,
+                            uint32_t* d_out, uint32_t grid_cap,
+                            hipStream_t stream);
+// d_out[m] = zlib crc32 of base[d_offs[m], d_offs[m] + d_lens[m]), any
+// offset, any length.
+hipError_t rocp2p_crc32_msgs_b(const void* base, const uint64_t* d_offs,
+                               const uint64_t* d_lens, uint32_t n,
+                               uint64_t max_msg_bytes, uint64_t* d_cstart,
+                               uint32_t* d_out, uint32_t grid_cap,
+                               hipStream_t stream);
+
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include "p2p_crc.h"
 #include "p2p_pattern.h"
 #include "p2p_varlen.h"
+#include "p2p_bytes.h"
 
 #define WAVE 64u
 #define PAGE 4096u
@@ -978,6 +979,418 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs_v(
 }
 
 // ---------------------------------------------------------------------
+// Byte-granular batches: lens[m] is any byte count and both addresses of
+// a message are any byte address, as an RDMA write's are.  The geometry
+// is p2p_bytes.h's: a message is cut on the 16-byte granule grid of the
+// side that is WRITTEN, a chunk is 256 of those granules, and the chunk
+// count therefore depends on the store-side skew (dst & 15) as well as
+// on the length — k_vl_scan_b reads both.  Runs, the one binary search,
+// the forward cursor, the running CRC, the end-of-run shift and the
+// pending-share merge are k_msg_engine_v's, unchanged.
+//
+// The side that is read is loaded as aligned 16-byte granules too and
+// realigned in registers by rel = (src - dst) & 15, which is uniform
+// per message: rel == 0 is a scalar branch to load-and-store.  Otherwise
+// store granule q is cut from source granules q and q + 1; a lane takes
+// q + 1 from the next lane, lane 63 from lane 0's next piece, and lane 0
+// loads the one granule (256) the chunk needs beyond its own — every
+// source granule crosses the link once per chunk, in the same 1 KiB
+// contiguous wave loads as before.
+//
+// A chunk takes whole-granule accesses only if it is full on BOTH sides
+// (rocp2p_b_full): with rel != 0 a chunk whose store granules all lie
+// inside the message may still be cut from a source granule that holds
+// bytes in front of or behind the message.  Every other chunk — at most
+// the first one and the last two of a message — takes the same route
+// with ranged accesses: a granule is loaded and stored only in the bytes
+// [lo, hi) that belong to the message, with naturally aligned 1-, 2-, 4-
+// and 8-byte accesses, never a read-modify-write (the rest of the
+// granule may be a neighbouring message that another wave is writing).
+// A granule outside the message is not touched at all.
+//
+// ICRC: crc(A || B) = shift(crc(A), |B|) ^ crc(B) holds for any cut, so
+// the granule grid serves as well as the 16-bytes-from-the-start grid.
+// Full chunks go through icrc_chunk_full on the realigned registers;
+// every granule of another chunk contributes the CRC of its valid bytes
+// shifted by the message bytes behind them, straight into the digest.
+// acc covers full chunks only and is flushed before anything else of
+// the message is accounted for.
+
+// k_vl_scan for the byte-granular grid: where[m] is the address (or the
+// offset from a 16-byte-aligned base) message m is written at.
+__global__ void __launch_bounds__(VL_SCAN_THREADS) k_vl_scan_b(
+    const uint64_t* __restrict__ lens, const uint64_t* __restrict__ where,
+    uint32_t n, uint64_t* __restrict__ cstart) {
+  __shared__ uint64_t s_wave[VL_SCAN_THREADS / WAVE];
+  const uint32_t lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const uint64_t per =
+      ((uint64_t)n + VL_SCAN_THREADS - 1) / VL_SCAN_THREADS * WAVE;
+  const uint64_t b = min(wv * per, (uint64_t)n);
+  const uint64_t e = min(b + per, (uint64_t)n);
+  uint64_t sum = 0;
+  for (uint64_t i = b + lane; i < e; i += WAVE)
+    sum += rocp2p_b_chunks((uint32_t)where[i] & 15u, lens[i]);
+  for (uint32_t o = WAVE / 2; o; o >>= 1) sum += __shfl_xor(sum, o, WAVE);
+  if (lane == 0) s_wave[wv] = sum;
+  __syncthreads();
+  uint64_t at = 0;  // chunks before the tile at hand
+  for (uint32_t w = 0; w < wv; w++) at += s_wave[w];
+  for (uint64_t i0 = b; i0 < e; i0 += WAVE) {  // uniform trip count
+    const uint64_t i = i0 + lane;
+    const uint64_t k =
+        i < e ? rocp2p_b_chunks((uint32_t)where[i] & 15u, lens[i]) : 0;
+    uint64_t inc = k;  // inclusive scan over the tile
+    for (uint32_t o = 1; o < WAVE; o <<= 1) {
+      uint64_t v = __shfl_up(inc, o, WAVE);
+      if (lane >= o) inc += v;
+    }
+    if (i < e) cstart[i] = at + inc - k;
+    at += __shfl(inc, WAVE - 1, WAVE);
+  }
+  // the last wave's segment ends at n: its carry is the total
+  if (threadIdx.x == VL_SCAN_THREADS - 1) cstart[n] = at;
+}
+
+// The granule the next lane holds; lane 63 gets lane 0's.
+__device__ __forceinline__ rocp2p_g16 g16_next_lane(const rocp2p_g16& a,
+                                                    uint32_t lane) {
+  const int from = (int)((lane + 1) & (WAVE - 1));
+  const rocp2p_g16 r = {__shfl(a.x, from, WAVE), __shfl(a.y, from, WAVE),
+                        __shfl(a.z, from, WAVE), __shfl(a.w, from, WAVE)};
+  return r;
+}
+
+// The four store granules of a lane (pieces l, l+64, l+128, l+192) from
+// its four source granules and e, the chunk's 257th source granule,
+// which lane 0 holds.  The successor of piece 64u + 63 is piece
+// 64(u + 1), lane 0's next register.
+__device__ __forceinline__ void g16_realign4(
+    const rocp2p_g16& a0, const rocp2p_g16& a1, const rocp2p_g16& a2,
+    const rocp2p_g16& a3, const rocp2p_g16& e, uint32_t rel, uint32_t lane,
+    rocp2p_g16& v0, rocp2p_g16& v1, rocp2p_g16& v2, rocp2p_g16& v3) {
+  const rocp2p_g16 r0 = g16_next_lane(a0, lane), r1 = g16_next_lane(a1, lane);
+  const rocp2p_g16 r2 = g16_next_lane(a2, lane), r3 = g16_next_lane(a3, lane);
+  const rocp2p_g16 r4 = g16_next_lane(e, lane);
+  // word by word: a ?: of two structs is a select of their addresses
+  // and would put them all in scratch
+  const bool last = lane == WAVE - 1;
+  auto pick = [last](const rocp2p_g16& wrap, const rocp2p_g16& next) {
+    const rocp2p_g16 r = {last ? wrap.x : next.x, last ? wrap.y : next.y,
+                          last ? wrap.z : next.z, last ? wrap.w : next.w};
+    return r;
+  };
+  v0 = rocp2p_b_realign(a0, pick(r1, r0), rel);
+  v1 = rocp2p_b_realign(a1, pick(r2, r1), rel);
+  v2 = rocp2p_b_realign(a2, pick(r3, r2), rel);
+  v3 = rocp2p_b_realign(a3, pick(r4, r3), rel);
+}
+
+// zlib crc32 of the bytes [lo, hi) of a granule, lo < hi
+__device__ __forceinline__ uint32_t crc_granule_range(
+    const rocp2p_crc_tab256* t, const rocp2p_g16& v, uint32_t lo,
+    uint32_t hi) {
+  uint64_t d0 = v.x | ((uint64_t)v.y << 32);
+  uint64_t d1 = v.z | ((uint64_t)v.w << 32);
+  if (lo >= 8) {
+    d0 = d1 >> (8 * (lo - 8));
+    d1 = 0;
+  } else if (lo) {
+    d0 = (d0 >> (8 * lo)) | (d1 << (64 - 8 * lo));
+    d1 >>= 8 * lo;
+  }
+  uint32_t rem = hi - lo, crc = 0xFFFFFFFFu;
+  if (rem >= 8) {
+    crc = rocp2p_crc_step8(t, crc, (uint32_t)d0, (uint32_t)(d0 >> 32));
+    d0 = d1;
+    rem -= 8;
+  }
+  if (rem >= 8) {  // all 16 bytes
+    crc = rocp2p_crc_step8(t, crc, (uint32_t)d0, (uint32_t)(d0 >> 32));
+    rem -= 8;
+  }
+  for (; rem; rem--, d0 >>= 8)
+    crc = t[0][(crc ^ (uint32_t)d0) & 0xff] ^ (crc >> 8);
+  return crc ^ 0xFFFFFFFFu;
+}
+
+__device__ __forceinline__ uint4 g16_u4(const rocp2p_g16& v) {
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// The message engine for any length at any address, with (ICRC) or
+// without the inline digest.  Same launch shape, descriptors and scratch
+// as k_msg_engine_v; cstart comes from k_vl_scan_b over the side that is
+// written.  Without ICRC no table is staged and no CRC work is done.
+template <bool GATHER, bool ICRC>
+__global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_b(
+    uint8_t* __restrict__ region, const uint64_t* __restrict__ offs,
+    const uint64_t* __restrict__ addrs, const uint64_t* __restrict__ lens,
+    const uint64_t* __restrict__ cstart, uint32_t n,
+    uint32_t* __restrict__ out) {
+  __shared__ vl_engine_lds<ICRC> s;
+  if constexpr (ICRC) {
+    for (uint32_t i = threadIdx.x; i < 2 * 4 * 256; i += blockDim.x)
+      (&s.t.shift16[0][0][0])[i] = (&c_crc.shift16[0][0][0])[i];
+    crc_stage_tables(s.t.t);
+  }
+
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv =
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const uint32_t nwv = blockDim.x / WAVE;
+  uint64_t c0, c1;
+  rocp2p_vl_run(cstart[n], (uint64_t)gridDim.x * nwv,
+                (uint64_t)blockIdx.x * nwv + wv, &c0, &c1);
+
+  rocp2p_vl_cursor cur = {0, 0, 0, 0};
+  // This message: where its store stream and its source stream start
+  // (both 16-byte aligned, p2p_bytes.h), how far into the store stream
+  // it begins, and how much further on it lies in the source stream.
+  const uint8_t* from0 = nullptr;
+  uint8_t* to0 = nullptr;
+  uint32_t skew = 0, rel = 0;
+  auto open_msg = [&](uint64_t msg) {
+    uint8_t* inside = region + offs[msg];
+    uint8_t* outside = reinterpret_cast<uint8_t*>(addrs[msg]);
+    const uint8_t* from = GATHER ? outside : inside;
+    uint8_t* to = GATHER ? inside : outside;
+    skew = (uint32_t)reinterpret_cast<uintptr_t>(to) & 15u;
+    rel = (uint32_t)(reinterpret_cast<uintptr_t>(from) -
+                     reinterpret_cast<uintptr_t>(to)) & 15u;
+    to0 = to - skew;
+    from0 = from - skew - rel;
+  };
+  if (c0 < c1) {
+    rocp2p_vl_seek(&cur, cstart, lens, n, c0);
+    open_msg(cur.m);
+  }
+  uint32_t acc = 0;  // crc of this run's full chunks of message m so far
+  uint32_t pend_f = 0, pend_m = 0;
+  const rocp2p_g16 none = {0, 0, 0, 0};
+
+  for (uint64_t c = c0; c < c1; c++) {
+    const uint64_t p0 = cur.ci * PAGE;      // of the store stream
+    const uint64_t end = skew + cur.len;    // of the message, likewise
+    const uint8_t* sp = from0 + p0;
+    uint8_t* dp = to0 + p0;
+    const bool full = rocp2p_b_full(skew, rel, cur.len, cur.ci);
+    // four named registers, not an array: see k_msg_engine_v
+    rocp2p_g16 v0, v1, v2, v3;
+    uint64_t done;  // store-stream bytes [.., done) are covered by acc
+    if (full) {
+      const rocp2p_g16* src = reinterpret_cast<const rocp2p_g16*>(sp);
+      if (rel == 0) {
+        v0 = src[lane];
+        v1 = src[lane + WAVE];
+        v2 = src[lane + 2 * WAVE];
+        v3 = src[lane + 3 * WAVE];
+      } else {
+        const rocp2p_g16 a0 = src[lane], a1 = src[lane + WAVE];
+        const rocp2p_g16 a2 = src[lane + 2 * WAVE], a3 = src[lane + 3 * WAVE];
+        rocp2p_g16 e = none;
+        if (lane == 0) e = src[4 * WAVE];
+        g16_realign4(a0, a1, a2, a3, e, rel, lane, v0, v1, v2, v3);
+      }
+      rocp2p_g16* dst = reinterpret_cast<rocp2p_g16*>(dp);
+      dst[lane] = v0;
+      dst[lane + WAVE] = v1;
+      dst[lane + 2 * WAVE] = v2;
+      dst[lane + 3 * WAVE] = v3;
+      if constexpr (ICRC)
+        acc = rocp2p_crc_apply(s.t.t.shift[5],
+                               rocp2p_crc_apply(s.t.t.shift[5], acc)) ^
+              icrc_chunk_full(s.t, g16_u4(v0), g16_u4(v1), g16_u4(v2),
+                              g16_u4(v3), lane);
+      done = p0 + PAGE;
+    } else {
+      const uint64_t g0 = cur.ci * ROCP2P_B_PER_CHUNK;
+      // the message in the source stream
+      const uint64_t sbeg = (uint64_t)skew + rel, send = end + rel;
+      auto fetch = [&](uint32_t q) {
+        uint32_t lo, hi;
+        rocp2p_b_range(sbeg, send, g0 + q, &lo, &hi);
+        return rocp2p_b_load(sp + ROCP2P_B_GRAN * q, lo, hi);
+      };
+      if (rel == 0) {
+        v0 = fetch(lane);
+        v1 = fetch(lane + WAVE);
+        v2 = fetch(lane + 2 * WAVE);
+        v3 = fetch(lane + 3 * WAVE);
+      } else {
+        const rocp2p_g16 a0 = fetch(lane), a1 = fetch(lane + WAVE);
+        const rocp2p_g16 a2 = fetch(lane + 2 * WAVE);
+        const rocp2p_g16 a3 = fetch(lane + 3 * WAVE);
+        rocp2p_g16 e = none;
+        if (lane == 0) e = fetch(4 * WAVE);
+        g16_realign4(a0, a1, a2, a3, e, rel, lane, v0, v1, v2, v3);
+      }
+      uint32_t x = 0;
+      auto put = [&](uint32_t q, const rocp2p_g16& v) {
+        uint32_t lo, hi;
+        rocp2p_b_range(skew, end, g0 + q, &lo, &hi);
+        if (lo < hi) {
+          rocp2p_b_store(dp + ROCP2P_B_GRAN * q, lo, hi, v);
+          if constexpr (ICRC)
+            x ^= rocp2p_crc_mulmod(
+                rocp2p_crc_xpow8(end - ((g0 + q) * ROCP2P_B_GRAN + hi),
+                                 c_crc.xpow8),
+                crc_granule_range(s.t.t.slice, v, lo, hi));
+        }
+      };
+      put(lane, v0);
+      put(lane + WAVE, v1);
+      put(lane + 2 * WAVE, v2);
+      put(lane + 3 * WAVE, v3);
+      if constexpr (ICRC) {
+        for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
+        if (lane == 0) atomicXor(&out[cur.m], x);
+      }
+      done = p0;  // acc (if any) ends where this chunk begins
+    }
+    if constexpr (ICRC) {
+      const bool msg_end = cur.ci + 1 == cur.cpm;
+      const bool run_end = c + 1 == c1;
+      if (msg_end || run_end || !full) {
+        if (acc) {  // a zero CRC contributes nothing wherever it sits
+          const uint64_t r = end - done;
+          uint32_t f = acc;
+          if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
+          if (run_end && !msg_end) {
+            pend_f = f;
+            pend_m = (uint32_t)cur.m;
+          } else if (lane == 0) {
+            atomicXor(&out[cur.m], f);
+          }
+        }
+        acc = 0;
+      }
+    }
+    if (c + 1 < c1 && rocp2p_vl_next(&cur, cstart, lens)) open_msg(cur.m);
+  }
+
+  if constexpr (ICRC) {
+    __syncthreads();  // the tables are dead: their first words hand off
+    vl_merge_pending(&s.t.t.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
+  }
+}
+
+// k_crc32_msgs_v for messages at any byte offset: message m is
+// base[offs[m], offs[m] + lens[m]), cut on the granule grid of
+// base + offs[m] (base is 16-byte aligned).  Chunks wholly inside the
+// message are aligned and go through crc_page; the first and the last
+// chunk use the flat identity over the chunk's valid bytes [lo, hi):
+// lane l owns [64l, 64l + 64) ∩ [lo, hi), loaded with rocp2p_b_load.
+__global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs_b(
+    const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
+    const uint64_t* __restrict__ lens, const uint64_t* __restrict__ cstart,
+    uint32_t n, uint32_t* __restrict__ out) {
+  __shared__ crc_lds s;
+  crc_stage_tables(s);
+
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv =
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const uint32_t nwv = blockDim.x / WAVE;
+  uint64_t c0, c1;
+  rocp2p_vl_run(cstart[n], (uint64_t)gridDim.x * nwv,
+                (uint64_t)blockIdx.x * nwv + wv, &c0, &c1);
+
+  rocp2p_vl_cursor cur = {0, 0, 0, 0};
+  const uint8_t* mp0 = base;  // where the message's stream starts
+  uint32_t skew = 0;
+  auto open_msg = [&](uint64_t msg) {
+    const uint64_t off = offs[msg];
+    skew = (uint32_t)off & 15u;
+    mp0 = base + (off - skew);
+  };
+  if (c0 < c1) {
+    rocp2p_vl_seek(&cur, cstart, lens, n, c0);
+    open_msg(cur.m);
+  }
+  uint32_t acc = 0;  // crc of this run's full chunks of message m so far
+  uint32_t pend_f = 0, pend_m = 0;
+
+  for (uint64_t c = c0; c < c1; c++) {
+    const uint64_t p0 = cur.ci * PAGE;    // of the message's stream
+    const uint64_t end = skew + cur.len;  // of the message, likewise
+    const uint8_t* seg = mp0 + p0 + lane * SEG;
+    const bool full = rocp2p_b_full(skew, 0, cur.len, cur.ci);
+    uint64_t done;  // stream bytes [.., done) are covered by acc
+    if (full) {
+      acc = rocp2p_crc_apply(s.shift[5], rocp2p_crc_apply(s.shift[5], acc)) ^
+            crc_page(seg, lane, s);
+      done = p0 + PAGE;
+    } else {
+      // the chunk's valid bytes, and this lane's [a, b) of its 64
+      const uint32_t lo = p0 < skew ? skew : 0u;  // first chunk only
+      const uint32_t hi = (uint32_t)min(end - p0, (uint64_t)PAGE);
+      const uint32_t beg = lane * SEG;
+      const uint32_t a = lo > beg ? min(lo - beg, SEG) : 0u;  // < 16
+      const uint32_t b = hi > beg ? min(hi - beg, SEG) : 0u;
+      uint32_t x = 0;
+      if (a < b) {
+        const uint64_t g0 = cur.ci * ROCP2P_B_PER_CHUNK + lane * 4;
+        uint64_t d[9];
+#pragma unroll
+        for (uint32_t q = 0; q < 4; q++) {
+          uint32_t glo, ghi;
+          rocp2p_b_range(skew, end, g0 + q, &glo, &ghi);
+          const rocp2p_g16 v =
+              rocp2p_b_load(seg + ROCP2P_B_GRAN * q, glo, ghi);
+          d[2 * q] = v.x | ((uint64_t)v.y << 32);
+          d[2 * q + 1] = v.z | ((uint64_t)v.w << 32);
+        }
+        d[8] = 0;
+        if (a) {  // bring byte a down to byte 0
+          if (a >= 8) {
+#pragma unroll
+            for (uint32_t i = 0; i < 8; i++) d[i] = d[i + 1];
+          }
+          const uint32_t sh = 8 * (a & 7);
+          if (sh) {
+#pragma unroll
+            for (uint32_t i = 0; i < 8; i++)
+              d[i] = (d[i] >> sh) | (d[i + 1] << (64 - sh));
+          }
+        }
+        uint32_t w[16];
+#pragma unroll
+        for (uint32_t i = 0; i < 8; i++) {
+          w[2 * i] = (uint32_t)d[i];
+          w[2 * i + 1] = (uint32_t)(d[i] >> 32);
+        }
+        x = rocp2p_crc_mulmod(
+            rocp2p_crc_xpow8(end - (p0 + beg + b), c_crc.xpow8),
+            crc_bytes64(s.slice, w, b - a));
+      }
+      for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
+      if (lane == 0) atomicXor(&out[cur.m], x);
+      done = p0;  // acc (if any) ends where this chunk begins
+    }
+    const bool msg_end = cur.ci + 1 == cur.cpm;
+    const bool run_end = c + 1 == c1;
+    if (msg_end || run_end || !full) {
+      if (acc) {  // a zero CRC contributes nothing wherever it sits
+        const uint64_t r = end - done;
+        uint32_t f = acc;
+        if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
+        if (run_end && !msg_end) {
+          pend_f = f;
+          pend_m = (uint32_t)cur.m;
+        } else if (lane == 0) {
+          atomicXor(&out[cur.m], f);
+        }
+      }
+      acc = 0;
+    }
+    if (c + 1 < c1 && rocp2p_vl_next(&cur, cstart, lens)) open_msg(cur.m);
+  }
+
+  __syncthreads();  // the tables are dead: their first words hand off
+  vl_merge_pending(&s.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
+}
+
+// ---------------------------------------------------------------------
 // launchers
 
 static inline uint32_t stream_grid(uint64_t items, uint32_t per_block) {
@@ -1343,6 +1756,114 @@ extern "C" hipError_t rocp2p_crc32_msgs_v(const void* base,
   const uint32_t grid =
       vl_grid(n, max_msg_bytes, CRC_DIGEST_WAVES, grid_cap ? grid_cap : 256);
   hipLaunchKernelGGL(k_crc32_msgs_v, dim3(grid),
+                     dim3(WAVE * CRC_DIGEST_WAVES), 0, stream,
+                     (const uint8_t*)base, d_offs, d_lens,
+                     (const uint64_t*)d_cstart, n, d_out);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------
+// Byte-granular launchers: those of the variable-length forms with
+// k_vl_scan_b over the side that is written.  A skewed message of
+// max_msg_bytes may have one chunk more than an aligned one (b_bound);
+// like max_msg_bytes itself that only sizes the grid.  The grid caps are
+// msg_engine_v_launch's until measurements say otherwise
+// (docs/PERF.md).
+
+static uint64_t b_bound(uint64_t max_msg_bytes) {
+  return max_msg_bytes ? max_msg_bytes + PAGE : 0;
+}
+
+static hipError_t vl_scan_b_launch(const uint64_t* d_lens,
+                                   const uint64_t* d_where, uint32_t n,
+                                   uint64_t* d_cstart, hipStream_t stream) {
+  hipLaunchKernelGGL(k_vl_scan_b, dim3(1), dim3(VL_SCAN_THREADS), 0, stream,
+                     d_lens, d_where, n, d_cstart);
+  return hipGetLastError();
+}
+
+template <bool GATHER>
+static hipError_t msg_engine_b_launch(void* region, const uint64_t* d_offs,
+                                      const uint64_t* d_addrs,
+                                      const uint64_t* d_lens, uint32_t n,
+                                      uint64_t max_msg_bytes,
+                                      uint64_t* d_cstart, uint32_t* d_out,
+                                      uint32_t grid_cap, hipStream_t stream) {
+  if (!d_cstart || (uintptr_t)region % 16) return hipErrorInvalidValue;
+  if (!n) return hipSuccess;
+  hipError_t e;
+  uint64_t cap = gather_grid_cap();
+  if (d_out) {
+    e = crc_tables_ready();
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+  }
+  const bool small = max_msg_bytes && max_msg_bytes < PAGE;
+  if ((d_out || (GATHER && !small)) && cap > ICRC_GRID) cap = ICRC_GRID;
+  if (grid_cap && grid_cap < cap) cap = grid_cap;
+  // the region base is 16-byte aligned: an offset's low bits are the skew
+  e = vl_scan_b_launch(d_lens, GATHER ? d_offs : d_addrs, n, d_cstart,
+                       stream);
+  if (e != hipSuccess) return e;
+  const uint32_t grid = vl_grid(n, b_bound(max_msg_bytes), ICRC_WAVES, cap);
+  if (d_out)
+    hipLaunchKernelGGL((k_msg_engine_b<GATHER, true>), dim3(grid),
+                       dim3(WAVE * ICRC_WAVES), 0, stream, (uint8_t*)region,
+                       d_offs, d_addrs, d_lens, (const uint64_t*)d_cstart, n,
+                       d_out);
+  else
+    hipLaunchKernelGGL((k_msg_engine_b<GATHER, false>), dim3(grid),
+                       dim3(WAVE * ICRC_WAVES), 0, stream, (uint8_t*)region,
+                       d_offs, d_addrs, d_lens, (const uint64_t*)d_cstart, n,
+                       d_out);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rocp2p_gather_b(void* dst_base,
+                                      const uint64_t* d_dst_offs,
+                                      const uint64_t* d_src_addrs,
+                                      const uint64_t* d_lens, uint32_t n,
+                                      uint64_t max_msg_bytes,
+                                      uint64_t* d_cstart, uint32_t* d_out,
+                                      uint32_t grid_cap, hipStream_t stream) {
+  return msg_engine_b_launch<true>(dst_base, d_dst_offs, d_src_addrs, d_lens,
+                                   n, max_msg_bytes, d_cstart, d_out,
+                                   grid_cap, stream);
+}
+
+extern "C" hipError_t rocp2p_scatter_b(const void* src_base,
+                                       const uint64_t* d_src_offs,
+                                       const uint64_t* d_dst_addrs,
+                                       const uint64_t* d_lens, uint32_t n,
+                                       uint64_t max_msg_bytes,
+                                       uint64_t* d_cstart, uint32_t* d_out,
+                                       uint32_t grid_cap,
+                                       hipStream_t stream) {
+  // the scatter instantiations only read the region
+  return msg_engine_b_launch<false>(const_cast<void*>(src_base), d_src_offs,
+                                    d_dst_addrs, d_lens, n, max_msg_bytes,
+                                    d_cstart, d_out, grid_cap, stream);
+}
+
+extern "C" hipError_t rocp2p_crc32_msgs_b(const void* base,
+                                          const uint64_t* d_offs,
+                                          const uint64_t* d_lens, uint32_t n,
+                                          uint64_t max_msg_bytes,
+                                          uint64_t* d_cstart, uint32_t* d_out,
+                                          uint32_t grid_cap,
+                                          hipStream_t stream) {
+  if (!d_cstart || (uintptr_t)base % 16) return hipErrorInvalidValue;
+  if (!n) return hipSuccess;
+  hipError_t e = crc_tables_ready();
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+  if (e != hipSuccess) return e;
+  e = vl_scan_b_launch(d_lens, d_offs, n, d_cstart, stream);
+  if (e != hipSuccess) return e;
+  const uint32_t grid = vl_grid(n, b_bound(max_msg_bytes), CRC_DIGEST_WAVES,
+                                grid_cap ? grid_cap : 256);
+  hipLaunchKernelGGL(k_crc32_msgs_b, dim3(grid),
                      dim3(WAVE * CRC_DIGEST_WAVES), 0, stream,
                      (const uint8_t*)base, d_offs, d_lens,
                      (const uint64_t*)d_cstart, n, d_out);

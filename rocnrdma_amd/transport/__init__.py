@@ -49,6 +49,10 @@ def get_transport(name: str, **kw) -> Transport:
             raise NotImplementedError(
                 "verbs transport does not implement icrc=True (an HCA "
                 "checks its own ICRC)")
+        if kw.get("byte_granular"):
+            raise NotImplementedError(
+                "verbs transport does not implement byte_granular=True "
+                "(the native harness posts fixed-size work requests)")
         if kw.get("var_len"):
             raise NotImplementedError(
                 "verbs transport does not implement var_len=True (the "

@@ -30,6 +30,16 @@ becomes the slot size, message i still goes to region offset
 nbytes (0 <= nbytes <= msg_bytes, a multiple of 16) of the slot and of
 the region message; the rest of both is untouched.
 `digest_check(payload, lens)` audits such traffic, slack included.
+
+`byte_granular=True` (opt-in on top of var_len=True, backends that
+support it) removes the "16": nbytes may be any integer in range, and
+the constructor arguments `region_skew` / `staging_skew` (each in
+[0, 16), constant per transport) start message i that many bytes into
+its region message and into its staging slot, so that the two sides may
+be misaligned against each other by any amount.  nbytes + skew <=
+msg_bytes holds on both sides; nbytes=None means the most that fits.
+Only nbytes bytes move; the whole rest of the slot, in front of and
+behind the message, is slack that digest_check(payload, lens) audits.
 """
 from __future__ import annotations
 
@@ -40,16 +50,35 @@ class Transport(abc.ABC):
     name = "base"
     supports_icrc = False
     supports_var_len = False
+    supports_byte_granular = False
 
     def __init__(self, msg_bytes: int, region_bytes: int,
                  inflight: int | None = 8, direction: str = "write",
-                 icrc: bool = False, var_len: bool = False, **_):
+                 icrc: bool = False, var_len: bool = False,
+                 byte_granular: bool = False, region_skew: int = 0,
+                 staging_skew: int = 0, **_):
         if icrc and not self.supports_icrc:
             raise NotImplementedError(
                 f"{self.name} transport does not implement icrc=True")
+        if byte_granular and not self.supports_byte_granular:
+            raise NotImplementedError(
+                f"{self.name} transport does not implement "
+                "byte_granular=True")
         if var_len and not self.supports_var_len:
             raise NotImplementedError(
                 f"{self.name} transport does not implement var_len=True")
+        if byte_granular and not var_len:
+            raise ValueError("byte_granular=True needs var_len=True: only "
+                             "a post that carries its own byte count can "
+                             "carry an odd one")
+        for what, skew in (("region_skew", region_skew),
+                           ("staging_skew", staging_skew)):
+            if int(skew) != skew or not 0 <= skew < 16:
+                raise ValueError(f"{what} must be an integer in [0, 16)")
+            if skew and not byte_granular:
+                raise ValueError(f"{what} needs byte_granular=True")
+        if max(region_skew, staging_skew) >= msg_bytes:
+            raise ValueError("skew leaves no room in a slot of msg_bytes")
         if region_bytes % msg_bytes:
             raise ValueError("region must be a multiple of msg size")
         if direction not in ("write", "read"):
@@ -62,6 +91,12 @@ class Transport(abc.ABC):
         self.direction = direction
         self.icrc = bool(icrc)
         self.var_len = bool(var_len)
+        self.byte_granular = bool(byte_granular)
+        self.region_skew = int(region_skew)
+        self.staging_skew = int(staging_skew)
+        # the longest message a slot holds behind the larger skew
+        self.max_nbytes = msg_bytes - max(self.region_skew,
+                                          self.staging_skew)
 
     # -- data plane ----------------------------------------------------
     @abc.abstractmethod
@@ -89,7 +124,9 @@ class Transport(abc.ABC):
 
     def _lens(self, nbytes, n: int):
         """nbytes of n posts as a validated int64 array (None = full
-        slots): 0 <= nbytes <= msg_bytes, multiples of 16."""
+        slots): 0 <= nbytes <= msg_bytes, multiples of 16.  With
+        byte_granular any integer 0 <= nbytes <= max_nbytes (msg_bytes
+        less the larger skew; None = max_nbytes)."""
         import numpy as np
 
         if not self.var_len:
@@ -97,7 +134,7 @@ class Transport(abc.ABC):
                 f"nbytes needs a transport opened with var_len=True "
                 f"(this {self.name} transport moves msg_bytes per message)")
         if nbytes is None:
-            return np.full(n, self.msg_bytes, dtype=np.int64)
+            return np.full(n, self.max_nbytes, dtype=np.int64)
         arr = np.asarray(nbytes)
         if arr.dtype.kind not in "iu":
             raise ValueError("nbytes must be integers")
@@ -108,6 +145,12 @@ class Transport(abc.ABC):
         if arr.dtype.kind == "u" and arr.size and int(arr.max()) > self.msg_bytes:
             raise ValueError("nbytes above msg_bytes")
         arr = arr.astype(np.int64)
+        if self.byte_granular:
+            if ((arr < 0) | (arr > self.max_nbytes)).any():
+                raise ValueError(
+                    f"nbytes must be in [0, {self.max_nbytes}] (msg_bytes "
+                    "less the larger skew)")
+            return arr
         if ((arr < 0) | (arr > self.msg_bytes) | (arr % 16 != 0)).any():
             raise ValueError(
                 f"nbytes must be multiples of 16 in [0, {self.msg_bytes}]")
@@ -116,10 +159,16 @@ class Transport(abc.ABC):
     def _len1(self, nbytes) -> int:
         """_lens for one post, without numpy."""
         if nbytes is None:
-            return self.msg_bytes
+            return self.max_nbytes
         if not self.var_len:
             self._lens(nbytes, 1)  # raises
         ln = int(nbytes)
+        if self.byte_granular:
+            if ln != nbytes or not 0 <= ln <= self.max_nbytes:
+                raise ValueError(
+                    f"nbytes must be in [0, {self.max_nbytes}] (msg_bytes "
+                    "less the larger skew)")
+            return ln
         if ln != nbytes or not 0 <= ln <= self.msg_bytes or ln % 16:
             raise ValueError(
                 f"nbytes must be a multiple of 16 in [0, {self.msg_bytes}]")
@@ -143,7 +192,9 @@ class Transport(abc.ABC):
         side is set to a known byte first and every slack range
         [j * msg_bytes + lens[j], (j + 1) * msg_bytes) must still hold
         it afterwards: a message is bad if its digest differs or its
-        slack changed."""
+        slack changed.  With byte_granular the sender holds those bytes
+        at its skew and the slack is the whole slot outside
+        [skew, skew + lens[j]), in front of and behind the message."""
         raise NotImplementedError(
             f"{self.name} transport does not implement digest_check")
 
@@ -171,6 +222,13 @@ class Transport(abc.ABC):
                 "one digest per slot (or region message), taken before "
                 "the posts, and cannot know the length a later post will "
                 "carry; icrc=True still serves digest_check(payload, lens)")
+
+    def _no_pattern_with_skew(self) -> None:
+        if self.region_skew or self.staging_skew:
+            raise NotImplementedError(
+                "integrity_check moves whole slots of the fill pattern; a "
+                "transport with a skew is audited with "
+                "digest_check(payload, lens)")
 
     def _payload_bytes(self, payload):
         """payload as a flat contiguous uint8 numpy array of region_bytes."""

@@ -15,6 +15,7 @@ class FakeTransport(Transport):
     name = "fake"
     supports_icrc = True  # zlib on the host: the sdma logic, CPU tier
     supports_var_len = True
+    supports_byte_granular = True
     KNOWN = 0x5A  # what digest_check(payload, lens) leaves in the slack
 
     def __init__(self, msg_bytes: int, region_bytes: int, **kw):
@@ -28,8 +29,9 @@ class FakeTransport(Transport):
 
     def post(self, i: int, nbytes: int | None = None) -> None:
         ln = self._len1(nbytes)
-        slot = self.staging[i % self.inflight][:ln]
-        off = (i % self.msgs_per_region) * self.msg_bytes
+        ss = self.staging_skew
+        slot = self.staging[i % self.inflight][ss : ss + ln]
+        off = (i % self.msgs_per_region) * self.msg_bytes + self.region_skew
         dst = self.region[off : off + ln]
         if self.icrc:
             self._digest(i, slot if self.direction == "write" else dst)
@@ -69,6 +71,7 @@ class FakeTransport(Transport):
         return {"checked": self._checked, "bad": self._bad}
 
     def integrity_check(self, seed: int) -> int:
+        self._no_pattern_with_skew()
         if self.icrc:
             self._expected = None  # the sender is rewritten below
         ref = pattern.fill_reference(self.region_bytes, seed)
@@ -136,9 +139,11 @@ class FakeTransport(Transport):
                 self._inline = None
 
     def _digest_check_var(self, pay, lens) -> int:
-        """digest_check for per-message lengths: digests of the first
-        lens[j] bytes, and the receiver's slack must keep KNOWN."""
+        """digest_check for per-message lengths: digests of the lens[j]
+        bytes at the skew (0 unless byte_granular), and the receiver's
+        slack — the slot outside the message — must keep KNOWN."""
         n, msg = self.msgs_per_region, self.msg_bytes
+        ss, rs = self.staging_skew, self.region_skew
         write = self.direction == "write"
         if self.icrc:
             self._expected = None
@@ -151,10 +156,11 @@ class FakeTransport(Transport):
                 for i in range(n):
                     slot = self.staging[i % self.inflight]
                     slot[:] = pay[i * msg : (i + 1) * msg]
-                    sent[i] = zlib.crc32(slot[: lens[i]].tobytes())
+                    slot[ss : ss + lens[i]] = pay[i * msg : i * msg + lens[i]]
+                    sent[i] = zlib.crc32(slot[ss : ss + lens[i]].tobytes())
                     self.post(i, int(lens[i]))
                 self.flush()
-                offs = np.arange(n, dtype=np.int64) * msg
+                offs = np.arange(n, dtype=np.int64) * msg + rs
                 if self.icrc:
                     got = np.array(self._inline, np.uint32)
                 else:
@@ -162,22 +168,29 @@ class FakeTransport(Transport):
                         self.region, offs, lens)
                 bad |= got != sent
                 for i in range(n):
-                    slack = self.region[i * msg + lens[i] : (i + 1) * msg]
-                    bad[i] |= bool((slack != self.KNOWN).any())
+                    slot = self.region[i * msg : (i + 1) * msg]
+                    bad[i] |= bool((slot[:rs] != self.KNOWN).any() or
+                                   (slot[rs + lens[i]:] != self.KNOWN).any())
                 return int(bad.sum())
             # read: load the region, pull every message into a slot that
             # holds KNOWN, digest and inspect the slot
             self.region[:] = pay
+            if rs:
+                for i in range(n):
+                    self.region[i * msg + rs : i * msg + rs + lens[i]] = \
+                        pay[i * msg : i * msg + lens[i]]
             for i in range(n):
                 slot = self.staging[i % self.inflight]
                 slot[:] = self.KNOWN
                 self.post(i, int(lens[i]))
                 self.flush()
                 ln = int(lens[i])
-                got = zlib.crc32(slot[:ln].tobytes())
+                got = zlib.crc32(slot[ss : ss + ln].tobytes())
                 want = (self._inline[i] if self.icrc else
                         zlib.crc32(pay[i * msg : i * msg + ln].tobytes()))
-                bad[i] = got != want or bool((slot[ln:] != self.KNOWN).any())
+                bad[i] = (got != want or
+                          bool((slot[:ss] != self.KNOWN).any()) or
+                          bool((slot[ss + ln:] != self.KNOWN).any()))
             return int(bad.sum())
         finally:
             if self.icrc:

@@ -29,6 +29,11 @@ that — into two device counters.  No host readback, no extra sync.
 var_len=True (kernel engine only) gives every WQE a length word and
 retires the ring with ops.gather_v_/scatter_v_ (crc=icrc): msg_bytes is
 the slot size, each message moves only the bytes its post asked for.
+
+byte_granular=True (on top of var_len) retires the same ring with
+ops.gather_bytes_/scatter_bytes_: any byte count, and region_skew /
+staging_skew move every region offset and staging address of the ring
+by a constant, so the rows stay what they were.
 """
 from __future__ import annotations
 
@@ -52,6 +57,7 @@ class SdmaTransport(Transport):
     name = "sdma"
     supports_icrc = True
     supports_var_len = True
+    supports_byte_granular = True
 
     def __init__(self, msg_bytes: int, region_bytes: int, device=None,
                  num_streams: int = 2, engine: str = "auto",
@@ -95,7 +101,7 @@ class SdmaTransport(Transport):
         if self.engine == "kernel":
             import numpy as np
 
-            base = self.staging_flat.data_ptr()
+            base = self.staging_flat.data_ptr() + self.staging_skew
             self._slot_addr = [base + i * msg_bytes
                                for i in range(self.inflight)]
             self._slot_addr_np = np.array(self._slot_addr, dtype=np.int64)
@@ -128,7 +134,7 @@ class SdmaTransport(Transport):
     def post(self, i: int, nbytes: int | None = None) -> None:
         if nbytes is not None or self.var_len:
             nbytes = self._len1(nbytes)
-        off = (i % self.msgs_per_region) * self.msg_bytes
+        off = (i % self.msgs_per_region) * self.msg_bytes + self.region_skew
         slot = i % self.inflight
         if self.engine == "kernel":
             if self._pending >= self.inflight:
@@ -172,7 +178,8 @@ class SdmaTransport(Transport):
             idx = np.arange(start + done, start + done + take,
                             dtype=np.int64)
             self._desc_np[ROW_OFF, k:k + take] = \
-                (idx % self.msgs_per_region) * self.msg_bytes
+                (idx % self.msgs_per_region) * self.msg_bytes + \
+                self.region_skew
             self._desc_np[ROW_ADDR, k:k + take] = \
                 self._slot_addr_np[idx % self.inflight]
             if lens is not None:
@@ -235,8 +242,12 @@ class SdmaTransport(Transport):
         (flush) stream; with icrc the digests of the batch are kept."""
         from .. import ops
 
-        engine = (ops.gather_v_ if self.direction == "write"
-                  else ops.scatter_v_)
+        if self.byte_granular:
+            engine = (ops.gather_bytes_ if self.direction == "write"
+                      else ops.scatter_bytes_)
+        else:
+            engine = (ops.gather_v_ if self.direction == "write"
+                      else ops.scatter_v_)
         dig = engine(self.region, self._desc_dev[ROW_OFF, :n],
                      self._desc_dev[ROW_ADDR, :n],
                      self._desc_dev[self._row_len, :n],
@@ -276,6 +287,7 @@ class SdmaTransport(Transport):
     def integrity_check(self, seed: int) -> int:
         from .. import ops
 
+        self._no_pattern_with_skew()
         if self.icrc:
             self._stamped = False  # the sender is rewritten below
         ref = pattern.fill_reference(self.region_bytes, seed)
@@ -402,7 +414,9 @@ class SdmaTransport(Transport):
         zlib.  The receiver starts as _KNOWN everywhere and its slack
         ranges must still hold it: in HBM a second crc32_messages_v over
         the slack ranges against the digest of that many _KNOWN bytes,
-        on the host numpy."""
+        on the host numpy.  With byte_granular the messages sit at the
+        skews, the launches are crc32_messages_bytes and the slack is
+        the slot in front of and behind the message."""
         import zlib
 
         import numpy as np
@@ -410,14 +424,23 @@ class SdmaTransport(Transport):
         from .. import ops
 
         n, msg = self.msgs_per_region, self.msg_bytes
+        ss, rs = self.staging_skew, self.region_skew
+        crc_v = (ops.crc32_messages_bytes if self.byte_granular
+                 else ops.crc32_messages_v)
         write = self.direction == "write"
         if self.icrc:
             self._stamped = False
         offs = np.arange(n, dtype=np.int64) * msg
-        d_offs = torch.from_numpy(offs).to(self.device)
+        d_offs = torch.from_numpy(offs + rs).to(self.device)
         d_lens = torch.from_numpy(lens).to(self.device)
         if write:
             self.region.fill_(_KNOWN)
+        elif rs:
+            reg = pay_t.numpy().copy()
+            for j in range(n):
+                reg[j * msg + rs:j * msg + rs + lens[j]] = \
+                    pay_t.numpy()[j * msg:j * msg + lens[j]]
+            self.region.copy_(torch.from_numpy(reg))
         else:
             self.region.copy_(pay_t)
         torch.cuda.synchronize(self.device)
@@ -433,7 +456,10 @@ class SdmaTransport(Transport):
                 for j in range(i, i + burst):
                     slot = self.staging[j % self.inflight]
                     slot.copy_(pay_t[j * msg:(j + 1) * msg])
-                    host[j] = zlib.crc32(slot.numpy()[:lens[j]])
+                    if ss:
+                        slot[ss:ss + lens[j]].copy_(
+                            pay_t[j * msg:j * msg + lens[j]])
+                    host[j] = zlib.crc32(slot.numpy()[ss:ss + lens[j]])
             self.post_many(i, burst, lens[i:i + burst])
             self.flush()  # slots reused next burst: must complete
             if self.icrc:
@@ -441,22 +467,28 @@ class SdmaTransport(Transport):
             if not write:
                 for j in range(i, i + burst):
                     slot = self.staging[j % self.inflight].numpy()
-                    host[j] = zlib.crc32(slot[:lens[j]])
-                    bad[j] = bool((slot[lens[j]:] != _KNOWN).any())
+                    host[j] = zlib.crc32(slot[ss:ss + lens[j]])
+                    bad[j] = bool((slot[:ss] != _KNOWN).any() or
+                                  (slot[ss + lens[j]:] != _KNOWN).any())
             i += burst
         if self.icrc:
             hbm = torch.cat(inline)
         else:
-            hbm = ops.crc32_messages_v(self.region, d_offs, d_lens,
-                                       max_msg_bytes=msg)
+            hbm = crc_v(self.region, d_offs, d_lens, max_msg_bytes=msg)
         if write:
-            slack = ops.crc32_messages_v(self.region, d_offs + d_lens,
-                                         msg - d_lens, max_msg_bytes=msg)
+            behind = msg - rs - lens
+            slack = crc_v(self.region, d_offs + d_lens, msg - rs - d_lens,
+                          max_msg_bytes=msg)
             known = {int(k): zlib.crc32(bytes([_KNOWN]) * int(k))
-                     for k in np.unique(msg - lens)}
-            want = np.array([known[int(msg - ln)] for ln in lens],
+                     for k in np.unique(behind)}
+            want = np.array([known[int(k)] for k in behind],
                             dtype=np.uint32)
             bad |= slack.cpu().numpy().view(np.uint32) != want
+            if rs:
+                front = crc_v(self.region, d_offs - rs,
+                              torch.full_like(d_lens, rs), max_msg_bytes=16)
+                bad |= (front.cpu().numpy().view(np.uint32)
+                        != zlib.crc32(bytes([_KNOWN]) * rs))
         bad |= hbm.cpu().numpy().view(np.uint32) != host
         return int(bad.sum())
 

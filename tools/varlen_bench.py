@@ -13,7 +13,20 @@ them alike; REPEATS repeats show the spread (min / median / max).
    byte-weighted expectation from the three uniform rates;
 3. crc32_messages_v against crc32_messages, 1 MiB messages, 1 GiB.
 
+--bytes measures the byte-granular path instead (gather_bytes_ /
+scatter_bytes_ / crc32_messages_bytes):
+
+4. co-aligned: aligned multiples of 16 through the byte path against
+   gather_v_/scatter_v_ on the same batches; the _v form is measured
+   three times, the spread of its three medians is the noise;
+5. skewed: the same sizes plus one byte at each --skew SRC,DST (default
+   5,5: store skew only, and 3,11: the source realigned as well);
+6. crc32_messages_bytes against crc32_messages_v, 1 MiB messages,
+   1 GiB, at offset skew 0 and 7.
+
 Usage: python tools/varlen_bench.py [--out profiles/varlen_1gpu.txt]
+       python tools/varlen_bench.py --bytes [--skew 5,5 --skew 3,11]
+                                    [--out profiles/bytes_1gpu.txt]
 """
 from __future__ import annotations
 
@@ -70,10 +83,147 @@ def fmt(r) -> str:
     return (f"{statistics.median(r):8.2f}  [{min(r):7.2f} .. {max(r):7.2f}]")
 
 
+def bytes_sections(say, dev, skews) -> None:
+    """Sections 4-6: the byte-granular path."""
+    slack = 2 << 20  # room for the skewed layouts
+    staging = torch.empty(STAGING + slack, dtype=torch.uint8,
+                          pin_memory=True)
+    staging.numpy()[:] = np.random.default_rng(1).integers(
+        0, 256, staging.numel(), dtype=np.uint8)
+    region = torch.zeros(STAGING + slack, dtype=torch.uint8, device=dev)
+    base = staging.data_ptr()
+    assert base % 16 == 0 and region.data_ptr() % 16 == 0
+
+    def dev64(a):
+        return torch.from_numpy(np.asarray(a, dtype=np.int64)).to(dev)
+
+    def engines(offs, addrs, lens, cap, which):
+        g, sc = ((ops.gather_v_, ops.scatter_v_) if which == "v"
+                 else (ops.gather_bytes_, ops.scatter_bytes_))
+        return {
+            "gather": lambda: g(region, offs, addrs, lens,
+                                max_msg_bytes=cap),
+            "gather(crc)": lambda: g(region, offs, addrs, lens,
+                                     max_msg_bytes=cap, crc=True),
+            "scatter": lambda: sc(region, offs, addrs, lens,
+                                  max_msg_bytes=cap),
+            "scatter(crc)": lambda: sc(region, offs, addrs, lens,
+                                       max_msg_bytes=cap, crc=True),
+        }
+
+    say()
+    say("## 4. co-aligned multiples of 16: gather_bytes_/scatter_bytes_ "
+        "against gather_v_/scatter_v_")
+    say("_v is measured three times (a, b, c); noise = spread of its "
+        "three medians; ratio = bytes / median of the three")
+    say(f"{'msg':>8} {'batch':>6} {'variant':<14} {'_v a/b/c GB/s':<26} "
+        f"{'noise':>6} {'bytes GB/s':>10}  {'[min .. max]':<20} ratio")
+    for msg in SIZES:
+        n = batch_of(msg)
+        offs = dev64(np.arange(n) * msg)
+        addrs = dev64(base + np.arange(n) * msg)
+        lens = dev64(np.full(n, msg))
+        old = engines(offs, addrs, lens, msg, "v")
+        new = engines(offs, addrs, lens, msg, "bytes")
+        variants = {}
+        for k in old:
+            for rep in "abc":
+                variants[f"{k}/v{rep}"] = old[k]
+            variants[f"{k}/bytes"] = new[k]
+        rates = measure(variants, n * msg)
+        for k in old:
+            meds = [statistics.median(rates[f"{k}/v{rep}"]) for rep in "abc"]
+            noise = max(meds) - min(meds)
+            r = rates[f"{k}/bytes"]
+            ratio = statistics.median(r) / statistics.median(meds)
+            say(f"{msg:>8} {n:>6} {k:<14} "
+                f"{meds[0]:8.2f} {meds[1]:8.2f} {meds[2]:8.2f} "
+                f"{noise:6.2f} {fmt(r)} {ratio:5.3f}")
+
+    # what the two-input scan costs: an all-zero batch through both
+    n = MAX_BATCH
+    offs, addrs = dev64(np.arange(n) * 64), dev64(base + np.arange(n) * 64)
+    zeros = dev64(np.zeros(n))
+    for name, fn in (("gather_v_", ops.gather_v_),
+                     ("gather_bytes_", ops.gather_bytes_)):
+        def call(fn=fn):
+            fn(region, offs, addrs, zeros, max_msg_bytes=64)
+        call()
+        torch.cuda.synchronize()
+        t = [time_ms(call, 200) for _ in range(REPEATS)]
+        say(f"scan + empty engine launch, {name}, n = {n} zero-length "
+            f"messages: {statistics.median(t) * 1e3:.1f} us per call "
+            f"[{min(t) * 1e3:.1f} .. {max(t) * 1e3:.1f}]")
+
+    say()
+    say("## 5. skewed: msg + 1 bytes, source at SRC and destination at "
+        "DST bytes past a 16-byte boundary")
+    say(f"{'skew':>6} {'msg':>8} {'batch':>6} {'variant':<14} {'GB/s':>8}  "
+        f"{'[min .. max]':<20}")
+    for src_skew, dst_skew in skews:
+        for msg in SIZES:
+            ln = msg + 1
+            n = batch_of(msg)
+            stride = (ln + 15) // 16 * 16 + 16
+            assert n * stride + 16 <= STAGING + slack
+            inside = np.arange(n) * stride
+            # gather writes the region, scatter the staging buffer: give
+            # each direction SRC on the side it reads, DST on the other
+            for which, o_sk, a_sk in (("gather", dst_skew, src_skew),
+                                      ("scatter", src_skew, dst_skew)):
+                fns = engines(dev64(inside + o_sk),
+                              dev64(base + inside + a_sk),
+                              dev64(np.full(n, ln)), ln, "bytes")
+                variants = {k: f for k, f in fns.items()
+                            if k.startswith(which)}
+                rates = measure(variants, n * ln)
+                for k in variants:
+                    say(f"{src_skew:>3},{dst_skew:<2} {ln:>8} {n:>6} "
+                        f"{k:<14} {fmt(rates[k])}")
+
+    say()
+    say("## 6. crc32_messages_bytes / crc32_messages_v, 1 MiB messages, "
+        "1 GiB")
+    del region
+    big = torch.empty((1 << 30) + 16, dtype=torch.uint8, device=dev)
+    ops.fill_(big[:1 << 30], 7)
+    msg, n = 1 << 20, 1 << 10
+    lens = dev64(np.full(n, msg))
+    offs0, offs7 = dev64(np.arange(n) * msg), dev64(np.arange(n) * msg + 7)
+    variants = {
+        "crc32_messages_v": lambda: ops.crc32_messages_v(
+            big, offs0, lens, max_msg_bytes=msg),
+        "bytes, skew 0": lambda: ops.crc32_messages_bytes(
+            big, offs0, lens, max_msg_bytes=msg),
+        "bytes, skew 7": lambda: ops.crc32_messages_bytes(
+            big, offs7, lens, max_msg_bytes=msg),
+    }
+    assert torch.equal(variants["crc32_messages_v"](),
+                       variants["bytes, skew 0"]())
+    rates = measure(variants, 1 << 30)
+    ref = statistics.median(rates["crc32_messages_v"])
+    for name in variants:
+        say(f"{name:<18} {fmt(rates[name])}  "
+            f"ratio {statistics.median(rates[name]) / ref:5.3f}")
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/varlen_1gpu.txt")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--bytes", action="store_true",
+                    help="measure the byte-granular path (sections 4-6)")
+    ap.add_argument("--skew", action="append", default=None,
+                    metavar="SRC,DST",
+                    help="with --bytes: a (source, destination) skew pair "
+                         "for section 5; repeatable")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = ("profiles/bytes_1gpu.txt" if args.bytes
+                    else "profiles/varlen_1gpu.txt")
+    skews = [tuple(int(v) for v in s.split(","))
+             for s in (args.skew or ["5,5", "3,11"])]
+    if any(len(p) != 2 or not all(0 <= v < 16 for v in p) for p in skews):
+        ap.error("--skew takes SRC,DST with both in [0, 16)")
     assert torch.cuda.is_available(), "varlen_bench needs a GPU"
     dev = torch.device("cuda", 0)
     lines = []
@@ -81,6 +231,18 @@ def main() -> int:
     def say(s=""):
         print(s, flush=True)
         lines.append(s)
+
+    if args.bytes:
+        say(f"# tools/varlen_bench.py --bytes on "
+            f"{torch.cuda.get_device_name(dev)}; GB/s = 1e9 bytes/s moved "
+            f"(one direction), median [min .. max] of {REPEATS} repeats, "
+            f"device events")
+        bytes_sections(say, dev, skews)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)),
+                    exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return 0
 
     say(f"# tools/varlen_bench.py on {torch.cuda.get_device_name(dev)}; "
         f"GB/s = 1e9 bytes/s moved (one direction), median "
