@@ -5,7 +5,7 @@ deploy candidate; the GPU test tier runs a short bounded pass).
 
 CLI: python -m rocnrdma_amd.harness.soak [--secs 30] [--transport auto]
                                          [--audit pattern|crc] [--mixed]
-                                         [--bytes]
+                                         [--bytes] [--sg K]
 Exit nonzero on any integrity failure.
 """
 from __future__ import annotations
@@ -38,11 +38,49 @@ def mixed_lens(rng: random.Random, n: int, msg: int, unit: int = 16):
     return lens
 
 
+def mixed_sges(rng: random.Random, n: int, msg: int, max_sge: int,
+               room: int, disjoint: bool):
+    """n seeded scatter/gather lists for a slot of msg bytes, as an
+    int64 array (n, max_sge, 2) of (slot_off, nbytes): every list has a
+    seeded number of SGEs in [0, max_sge] (the others stay at length 0,
+    anywhere in the list), their lengths are a seeded cut of a
+    mixed_lens total of at most room bytes — so empty and 1-byte SGEs
+    and whole-slot messages all occur — and their offsets are seeded:
+    disjoint ranges in a shuffled order of the slot (what a read needs),
+    or anywhere in the slot, overlaps included."""
+    import numpy as np
+
+    g = np.random.default_rng(rng.getrandbits(32))
+    total = mixed_lens(rng, n, room, 1)
+    sges = np.zeros((n, max_sge, 2), dtype=np.int64)
+    for i in range(n):
+        used = np.sort(g.permutation(max_sge)[:g.integers(0, max_sge + 1)])
+        if not used.size:
+            continue
+        cuts = np.sort(g.integers(0, total[i] + 1, used.size - 1))
+        if used.size > 1 and g.random() < 0.3:
+            cuts[0] = min(1, total[i])  # a 1-byte SGE in front
+            cuts.sort()
+        lens = np.diff(np.concatenate([[0], cuts, [total[i]]]))
+        sges[i, used, 1] = lens
+        if disjoint:
+            # spread the free bytes of the slot over the gaps, then lay
+            # the SGEs out in a shuffled order
+            order = g.permutation(used.size)
+            gaps = np.diff(np.concatenate(
+                [[0], np.sort(g.integers(0, msg - total[i] + 1, used.size))]))
+            at = np.cumsum(gaps + np.concatenate([[0], lens[order][:-1]]))
+            sges[i, used[order], 0] = at
+        else:
+            sges[i, used, 0] = g.integers(0, msg - lens + 1)
+    return sges
+
+
 def run_soak(transport: str = "auto", secs: float = 10.0,
              region_bytes: int = 256 << 20, seed: int = 1234,
              device=None, metrics=None, audit: str = "pattern",
              icrc: bool = False, mixed: bool = False,
-             byte_granular: bool = False) -> dict:
+             byte_granular: bool = False, sg: int = 0) -> dict:
     """audit="pattern": splitmix64 pattern + integrity_check (default).
     audit="crc": a seeded random payload per cycle through digest_check
     (per-message CRC32, content-independent).
@@ -57,7 +95,11 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
     are used by the audit only.
     byte_granular=True (needs mixed): the transport is opened with
     byte_granular=True and a seeded region_skew / staging_skew per cycle,
-    and the lengths are drawn from all byte counts that fit."""
+    and the lengths are drawn from all byte counts that fit.
+    sg=K > 1 (needs byte_granular): the transport is opened with
+    max_sge=K and staging_skew 0, every post carries a seeded
+    scatter/gather list (mixed_sges) and the audit is
+    digest_check_sg(payload, sges)."""
     from rocnrdma_amd.harness.sweep import pattern_sender
     from rocnrdma_amd.transport import get_transport
 
@@ -65,6 +107,11 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
         raise ValueError(f"audit must be 'pattern' or 'crc', not {audit!r}")
     if byte_granular and not mixed:
         raise ValueError("byte_granular=True needs mixed=True")
+
+    if sg and sg < 2:
+        raise ValueError("sg must be 0 (off) or a max_sge of at least 2")
+    if sg and not byte_granular:
+        raise ValueError("sg needs mixed=True and byte_granular=True")
 
     if metrics is None:
         from rocnrdma_amd.utils.metrics import TransferMetrics
@@ -87,6 +134,8 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
         if byte_granular:
             extra.update(byte_granular=True, region_skew=rng.randrange(16),
                          staging_skew=rng.randrange(16))
+        if sg:
+            extra.update(max_sge=sg, staging_skew=0)
         tp = get_transport(transport, msg_bytes=msg, region_bytes=region,
                            direction=direction, device=device, **extra)
         try:
@@ -148,6 +197,8 @@ def _mixed_cycle(tp, rng: random.Random, region: int):
     moved, messages moved, bad messages of the audit)."""
     import numpy as np
 
+    if tp.max_sge > 1:
+        return _sg_cycle(tp, rng, region)
     unit = 1 if tp.byte_granular else 16
     moved = posted = 0
     for _ in range(rng.randint(1, 4)):
@@ -162,6 +213,30 @@ def _mixed_cycle(tp, rng: random.Random, region: int):
     lens = mixed_lens(rng, tp.msgs_per_region, tp.max_nbytes, unit)
     bad = tp.digest_check(payload, lens)
     return (moved + int(lens.sum()), posted + tp.msgs_per_region, bad)
+
+
+def _sg_cycle(tp, rng: random.Random, region: int):
+    """_mixed_cycle with a seeded scatter/gather list per message."""
+    import numpy as np
+
+    room = tp.msg_bytes - tp.region_skew
+    disjoint = tp.direction == "read"  # the side that is written
+    moved = posted = 0
+    for _ in range(rng.randint(1, 4)):
+        burst = rng.randint(1, max(2, tp.inflight))
+        sges = mixed_sges(rng, burst, tp.msg_bytes, tp.max_sge, room,
+                          disjoint)
+        tp.post_many_sg(posted, burst, sges)
+        posted += burst
+        moved += int(sges[:, :, 1].sum())
+        tp.flush()
+    payload = np.random.default_rng(rng.getrandbits(32)).integers(
+        0, 256, region, dtype=np.uint8)
+    sges = mixed_sges(rng, tp.msgs_per_region, tp.msg_bytes, tp.max_sge,
+                      room, disjoint)
+    bad = tp.digest_check_sg(payload, sges)
+    return (moved + int(sges[:, :, 1].sum()), posted + tp.msgs_per_region,
+            bad)
 
 
 def main():
@@ -185,6 +260,10 @@ def main():
                     help="with --mixed: byte-granular traffic, lengths "
                          "from all byte counts (not multiples of 16) at a "
                          "random skew per side")
+    ap.add_argument("--sg", type=int, default=0, metavar="K",
+                    help="with --mixed --bytes: scatter/gather traffic, "
+                         "up to K SGEs per message in seeded layouts, "
+                         "audited with digest_check_sg")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="expose Prometheus metrics on this port")
     args = ap.parse_args()
@@ -194,7 +273,7 @@ def main():
     stats = run_soak(args.transport, args.secs, args.region_bytes,
                      args.seed, metrics=metrics, audit=args.audit,
                      icrc=args.icrc, mixed=args.mixed,
-                     byte_granular=args.byte_granular)
+                     byte_granular=args.byte_granular, sg=args.sg)
     print(stats)
     raise SystemExit(1 if stats["failures"] else 0)
 

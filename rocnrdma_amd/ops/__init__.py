@@ -180,6 +180,47 @@ def crc32_messages_bytes(region: torch.Tensor, offs: torch.Tensor,
                                            max_msg_bytes, grid_cap)
 
 
+def gather_sg_(region: torch.Tensor, offs: torch.Tensor,
+               sge_start: torch.Tensor, sge_addrs: torch.Tensor,
+               sge_lens: torch.Tensor, *, max_msg_bytes: int = 0,
+               crc: bool = False, grid_cap: int = 0) -> torch.Tensor | None:
+    """gather_bytes_ for messages with a scatter/gather list, as a work
+    request's sg_list: the batch has n messages and S entries (SGEs) in
+    CSR form.  sge_start is int64[n + 1], nondecreasing from 0 to S;
+    message m owns the SGEs sge_start[m] .. sge_start[m + 1] - 1, SGE j
+    is the sge_lens[j] >= 0 bytes at the byte address sge_addrs[j]
+    (int64[S] each), and the message — their concatenation in list
+    order, L_m bytes — is written to region[offs[m] : offs[m] + L_m].
+    All four are contiguous int64 tensors on the region's device.  Any
+    address, offset and length; the misalignment is arbitrary per SGE
+    and only the region's base stays 16-byte aligned.  No byte outside
+    an SGE or outside a message's region range is loaded or stored
+    (narrow stores, never read-modify-write: consecutive SGEs and
+    neighbouring messages may share a granule).  Messages without SGEs
+    and SGEs of length 0 are legal anywhere and touch nothing.  SGEs may
+    overlap where they are read; overlap where they are written is
+    undefined.  With crc=True the result is zlib's CRC32 of every whole
+    message (int32 tensor[n], no sync; 0 for an empty one), however it
+    is cut — what gather_bytes_ returns for the same bytes as one
+    message; one SGE per message gives what gather_bytes_ gives.
+    max_msg_bytes bounds a whole message (0 = unknown) and only sizes
+    the grid; grid_cap as for gather_crc_.  Stream-ordered, no host
+    synchronise; the offsets are taken on the device."""
+    return _require().gather_sg_(region, offs, sge_start, sge_addrs,
+                                 sge_lens, max_msg_bytes, crc, grid_cap)
+
+
+def scatter_sg_(region: torch.Tensor, offs: torch.Tensor,
+                sge_start: torch.Tensor, sge_addrs: torch.Tensor,
+                sge_lens: torch.Tensor, *, max_msg_bytes: int = 0,
+                crc: bool = False, grid_cap: int = 0) -> torch.Tensor | None:
+    """scatter_bytes_ for messages with a scatter/gather list:
+    region[offs[m] : offs[m] + L_m] is cut, in list order, over the SGEs
+    of message m; see gather_sg_."""
+    return _require().scatter_sg_(region, offs, sge_start, sge_addrs,
+                                  sge_lens, max_msg_bytes, crc, grid_cap)
+
+
 def dmabuf_fd(buf: torch.Tensor) -> int:
     """Export an HBM tensor as a dmabuf fd (ibv_reg_dmabuf_mr's GPU
     half). Caller must os.close() the fd."""

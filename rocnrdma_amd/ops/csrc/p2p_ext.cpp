@@ -9,6 +9,7 @@
 #include <c10/cuda/CUDAGuard.h>
 
 #include "p2p_kernels.h"
+#include "p2p_sgl.h"  // ROCP2P_SGL_SCRATCH_WORDS
 
 namespace {
 
@@ -320,6 +321,73 @@ torch::Tensor crc32_messages_bytes(torch::Tensor region, torch::Tensor offs,
   return out;
 }
 
+// The scatter/gather forms (p2p_sgl.h): every host-visible argument
+// error raises before anything is launched; the scan scratch and the
+// digests are torch tensors like the _v forms'.
+template <typename Launch>
+c10::optional<torch::Tensor> msg_engine_sg(
+    const char* who, Launch launch, torch::Tensor region, torch::Tensor offs,
+    torch::Tensor sge_start, torch::Tensor sge_addrs, torch::Tensor sge_lens,
+    int64_t max_msg_bytes, bool crc, int64_t grid_cap) {
+  OnDeviceOf dev(region, who);
+  check_align16(region, who);
+  for (const torch::Tensor* t : {&offs, &sge_start, &sge_addrs, &sge_lens}) {
+    check_u64_dev(*t, who);
+    TORCH_CHECK(t->device() == region.device(), who,
+                ": descriptors must live on the region's device");
+  }
+  const int64_t n = offs.numel(), nsge = sge_lens.numel();
+  TORCH_CHECK(sge_start.numel() == n + 1, who,
+              ": sge_start must have n + 1 entries");
+  TORCH_CHECK(sge_addrs.numel() == nsge, who,
+              ": sge_addrs and sge_lens differ in length");
+  TORCH_CHECK(n < (1LL << 32) && nsge < (1LL << 32), who,
+              ": too many messages or SGEs");
+  TORCH_CHECK(max_msg_bytes >= 0, who, ": max_msg_bytes out of range");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= 0xffffffffLL, who,
+              ": grid_cap out of range");
+  auto scratch = torch::empty(
+      {(int64_t)ROCP2P_SGL_SCRATCH_WORDS(n, nsge)},
+      torch::dtype(torch::kInt64).device(region.device()));
+  c10::optional<torch::Tensor> out;
+  if (crc)
+    out = torch::empty({n},
+                       torch::dtype(torch::kInt32).device(region.device()));
+  HIP_OK(launch(region.data_ptr(), (const uint64_t*)offs.data_ptr<int64_t>(),
+                (const uint64_t*)sge_start.data_ptr<int64_t>(),
+                (const uint64_t*)sge_addrs.data_ptr<int64_t>(),
+                (const uint64_t*)sge_lens.data_ptr<int64_t>(), (uint32_t)n,
+                (uint32_t)nsge, (uint64_t)max_msg_bytes,
+                (uint64_t*)scratch.data_ptr<int64_t>(),
+                crc ? (uint32_t*)out->data_ptr<int32_t>() : nullptr,
+                (uint32_t)grid_cap, dev.stream));
+  return out;
+}
+
+c10::optional<torch::Tensor> gather_sg_(torch::Tensor region,
+                                        torch::Tensor dst_offs,
+                                        torch::Tensor sge_start,
+                                        torch::Tensor sge_addrs,
+                                        torch::Tensor sge_lens,
+                                        int64_t max_msg_bytes, bool crc,
+                                        int64_t grid_cap) {
+  return msg_engine_sg("gather_sg_", rocp2p_gather_sg, region, dst_offs,
+                       sge_start, sge_addrs, sge_lens, max_msg_bytes, crc,
+                       grid_cap);
+}
+
+c10::optional<torch::Tensor> scatter_sg_(torch::Tensor region,
+                                         torch::Tensor src_offs,
+                                         torch::Tensor sge_start,
+                                         torch::Tensor sge_addrs,
+                                         torch::Tensor sge_lens,
+                                         int64_t max_msg_bytes, bool crc,
+                                         int64_t grid_cap) {
+  return msg_engine_sg("scatter_sg_", rocp2p_scatter_sg, region, src_offs,
+                       sge_start, sge_addrs, sge_lens, max_msg_bytes, crc,
+                       grid_cap);
+}
+
 void copy_(torch::Tensor dst, torch::Tensor src) {
   OnDeviceOf dev(dst, "copy_");
   check_buf(src, "copy_");
@@ -407,6 +475,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "crc32_messages_v for offsets of any alignment",
         py::arg("region"), py::arg("offs"), py::arg("lens"),
         py::arg("max_msg_bytes") = 0, py::arg("grid_cap") = 0);
+  m.def("gather_sg_", &gather_sg_,
+        "gather_bytes_ for messages that are lists of outside buffers (CSR)",
+        py::arg("region"), py::arg("dst_offs"), py::arg("sge_start"),
+        py::arg("sge_addrs"), py::arg("sge_lens"),
+        py::arg("max_msg_bytes") = 0, py::arg("crc") = false,
+        py::arg("grid_cap") = 0);
+  m.def("scatter_sg_", &scatter_sg_,
+        "scatter_bytes_ for messages that are lists of outside buffers (CSR)",
+        py::arg("region"), py::arg("src_offs"), py::arg("sge_start"),
+        py::arg("sge_addrs"), py::arg("sge_lens"),
+        py::arg("max_msg_bytes") = 0, py::arg("crc") = false,
+        py::arg("grid_cap") = 0);
   m.def("dmabuf_fd", &dmabuf_fd,
         "export an HBM tensor range as a dmabuf fd (caller closes)");
 }

@@ -167,4 +167,47 @@ hipError_t rocp2p_crc32_msgs_b(const void* base, const uint64_t* d_offs,
                                uint32_t* d_out, uint32_t grid_cap,
                                hipStream_t stream);
 
+// Scatter/gather lists: the byte-granular engine for messages that are
+// the concatenation of several outside buffers, as a work request's
+// sg_list is (geometry and scratch layout: p2p_sgl.h).  The batch has n
+// messages and nsge scatter/gather entries (SGEs) in CSR form:
+// d_sge_start[n + 1] is nondecreasing from 0 to nsge, message m owns the
+// SGEs d_sge_start[m] .. d_sge_start[m + 1] - 1, SGE j is the
+// d_sge_lens[j] >= 0 bytes at the outside address d_sge_addrs[j].
+// gather_sg writes the SGEs of message m back to back to
+// base[d_offs[m], d_offs[m] + L_m), L_m the sum of their lengths;
+// scatter_sg cuts that range, in order, over the SGEs.  Any address, any
+// offset, any length; the relative misalignment is arbitrary per SGE and
+// only the base is 16-byte aligned.  No byte outside an SGE or outside
+// the region range of a message is loaded or stored, and partial
+// granules are written with narrow stores, never a read-modify-write:
+// consecutive SGEs and neighbouring messages may share a granule.  A
+// message without SGEs and an SGE of length 0 are legal anywhere and
+// reach no load, store or atomic.  SGEs may overlap on the side that is
+// read; overlap on the side that is written is undefined.
+// d_out: n digests (zeroed on `stream`), or null for no ICRC.  d_out[m]
+// is zlib's crc32 of the L_m message bytes however they are cut — what
+// the _b calls give for the same bytes as one message; 0 for an empty
+// message.  One SGE per message gives what the _b calls give.
+// d_scratch: ROCP2P_SGL_SCRATCH_WORDS(n, nsge) 64-bit words.
+// max_msg_bytes bounds a whole message (0 = unknown) and grid_cap caps
+// the workgroups as above; results depend on neither.  Stream-ordered
+// (a one-workgroup scan kernel, then the engine), allocate nothing, no
+// host synchronise.  hipErrorInvalidValue: null d_scratch, base not
+// 16-byte aligned.  n == 0 is a no-op; nsge == 0 only zeroes d_out.
+hipError_t rocp2p_gather_sg(void* dst_base, const uint64_t* d_dst_offs,
+                            const uint64_t* d_sge_start,
+                            const uint64_t* d_sge_addrs,
+                            const uint64_t* d_sge_lens, uint32_t n,
+                            uint32_t nsge, uint64_t max_msg_bytes,
+                            uint64_t* d_scratch, uint32_t* d_out,
+                            uint32_t grid_cap, hipStream_t stream);
+hipError_t rocp2p_scatter_sg(const void* src_base, const uint64_t* d_src_offs,
+                             const uint64_t* d_sge_start,
+                             const uint64_t* d_sge_addrs,
+                             const uint64_t* d_sge_lens, uint32_t n,
+                             uint32_t nsge, uint64_t max_msg_bytes,
+                             uint64_t* d_scratch, uint32_t* d_out,
+                             uint32_t grid_cap, hipStream_t stream);
+
 }  // extern "C"

@@ -31,6 +31,7 @@
 #include "p2p_pattern.h"
 #include "p2p_varlen.h"
 #include "p2p_bytes.h"
+#include "p2p_sgl.h"
 
 #define WAVE 64u
 #define PAGE 4096u
@@ -1391,6 +1392,268 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs_b(
 }
 
 // ---------------------------------------------------------------------
+// Scatter/gather lists (geometry: p2p_sgl.h).  A message is the
+// concatenation of its SGEs: a gather reads them from anywhere outside
+// and writes them back to back into the region, a scatter cuts the
+// contiguous region range over them.  The work item is the SGE.  A scan
+// kernel (k_sg_scan) turns the lists into what k_msg_engine_b takes per message —
+// the address written, the address read, the length, the chunk prefix
+// sums — plus the two things only the digest needs: the message that
+// owns the SGE and the message bytes behind it.  The engine then is
+// k_msg_engine_b over SGEs; consecutive SGEs of a message meet inside a
+// granule of the region like neighbouring messages do, which the narrow
+// stores of p2p_bytes.h already allow.
+//
+// ICRC: a CRC piece of SGE j is shifted by the bytes behind it in the
+// SGE, as before, and by tail[j] more, and is XORed into out[owner[j]]:
+// crc(A || B) = shift(crc(A), |B|) ^ crc(B) does not care where a
+// message is cut.  A message without SGEs, and an SGE without bytes, own
+// no chunk and reach no load, store or atomic.
+
+// A scan of value(0 .. count - 1) by one workgroup of VL_SCAN_THREADS:
+// k_vl_scan's two passes, with the values parked in out between them so
+// that value() runs once per item (the same lane owns an item in both
+// passes).  Sums (MAX false) are exclusive, out[0 .. count] with the
+// total last; running maxima (MAX true) are inclusive, out[0 .. count).
+// Ends with a barrier: out is complete and s_wave free again.
+template <bool MAX, typename T, typename F>
+__device__ __forceinline__ void sg_block_scan(F value, uint64_t count, T* out,
+                                              T* s_wave) {
+  auto op = [](T a, T b) { return MAX ? (a > b ? a : b) : (T)(a + b); };
+  const uint32_t lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const uint64_t per = (count + VL_SCAN_THREADS - 1) / VL_SCAN_THREADS * WAVE;
+  const uint64_t b = min(wv * per, count);
+  const uint64_t e = min(b + per, count);
+  T sum = 0;
+  for (uint64_t i = b + lane; i < e; i += WAVE) {
+    const T k = value(i);
+    out[i] = k;
+    sum = op(sum, k);
+  }
+  for (uint32_t o = WAVE / 2; o; o >>= 1)
+    sum = op(sum, __shfl_xor(sum, o, WAVE));
+  if (lane == 0) s_wave[wv] = sum;
+  __syncthreads();
+  T at = 0;  // what the items before the tile at hand amount to
+  for (uint32_t w = 0; w < wv; w++) at = op(at, s_wave[w]);
+  for (uint64_t i0 = b; i0 < e; i0 += WAVE) {  // uniform trip count
+    const uint64_t i = i0 + lane;
+    const T k = i < e ? out[i] : 0;
+    T inc = k;  // inclusive scan over the tile
+    for (uint32_t o = 1; o < WAVE; o <<= 1) {
+      T v = __shfl_up(inc, o, WAVE);
+      if (lane >= o) inc = op(inc, v);
+    }
+    if (i < e) out[i] = MAX ? op(at, inc) : (T)(at + inc - k);
+    at = op(at, __shfl(inc, WAVE - 1, WAVE));
+  }
+  // the last wave's segment ends at count: its carry is the total
+  if (!MAX && threadIdx.x == VL_SCAN_THREADS - 1) out[count] = at;
+  __syncthreads();
+}
+
+// The scan pass of a scatter/gather batch: one workgroup, one launch.
+// Owners first: every message with SGEs writes its number at its first
+// SGE and a running maximum spreads it over the others (message numbers
+// grow with the SGE index) — no search per SGE.  Then the byte prefix
+// sums P, and last every SGE's work item from P (rocp2p_sgl_item) and
+// the chunk prefix sums.  nsge > 0.
+template <bool GATHER>
+__global__ void __launch_bounds__(VL_SCAN_THREADS) k_sg_scan(
+    const uint8_t* region, const uint64_t* __restrict__ offs,
+    const uint64_t* __restrict__ sge_start,
+    const uint64_t* __restrict__ sge_addrs,
+    const uint64_t* __restrict__ sge_lens, uint32_t n, uint32_t nsge,
+    uint64_t* scratch) {
+  __shared__ uint64_t s_wave[VL_SCAN_THREADS / WAVE];
+  __shared__ uint32_t s_own[VL_SCAN_THREADS / WAVE];
+  const rocp2p_sgl_view v = rocp2p_sgl_carve(scratch, nsge);
+  for (uint32_t j = threadIdx.x; j < nsge; j += VL_SCAN_THREADS)
+    v.owner[j] = 0;
+  __syncthreads();
+  for (uint32_t m = threadIdx.x; m < n; m += VL_SCAN_THREADS)
+    if (rocp2p_sgl_has_sges(sge_start, m)) v.owner[sge_start[m]] = m;
+  __syncthreads();
+  sg_block_scan<true>([&](uint64_t j) { return v.owner[j]; }, nsge, v.owner,
+                      s_own);
+  sg_block_scan<false>([&](uint64_t j) { return sge_lens[j]; }, nsge,
+                       v.prefix, s_wave);
+  const uint64_t base = reinterpret_cast<uintptr_t>(region);
+  sg_block_scan<false>(
+      [&](uint64_t j) {
+        return rocp2p_sgl_item(v, base, offs, sge_start, sge_addrs, j,
+                               GATHER);
+      },
+      nsge, v.cstart, s_wave);
+}
+
+// k_msg_engine_b with the SGE as its work item: the same launch shape,
+// run split, cursor and chunk bodies, over the nsge SGEs that k_sg_scan
+// laid out in scratch (rocp2p_sgl_view).  The scan has resolved the direction (to / from
+// are addresses), so a gather and a scatter are the same code here.
+// Every CRC contribution carries the SGE's tail as a further shift and
+// goes to the digest of the owning message; the pending merge keys on
+// the owner as well (owners are nondecreasing in the SGE index, so equal
+// targets stay adjacent).  Without ICRC no table is staged and no CRC
+// work is done.
+template <bool ICRC>
+__global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_sg(
+    const uint64_t* __restrict__ sge_lens, const uint64_t* __restrict__ cstart,
+    const uint64_t* __restrict__ sge_to, const uint64_t* __restrict__ sge_from,
+    const uint64_t* __restrict__ sge_tail,
+    const uint32_t* __restrict__ sge_owner, uint32_t nsge,
+    uint32_t* __restrict__ out) {
+  __shared__ vl_engine_lds<ICRC> s;
+  if constexpr (ICRC) {
+    for (uint32_t i = threadIdx.x; i < 2 * 4 * 256; i += blockDim.x)
+      (&s.t.shift16[0][0][0])[i] = (&c_crc.shift16[0][0][0])[i];
+    crc_stage_tables(s.t.t);
+  }
+
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv =
+      (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  const uint32_t nwv = blockDim.x / WAVE;
+  uint64_t c0, c1;
+  rocp2p_vl_run(cstart[nsge], (uint64_t)gridDim.x * nwv,
+                (uint64_t)blockIdx.x * nwv + wv, &c0, &c1);
+
+  rocp2p_vl_cursor cur = {0, 0, 0, 0};  // cur.m is an SGE here
+  // This SGE: its store and source streams as in k_msg_engine_b, the
+  // message bytes behind it and the message it belongs to.
+  const uint8_t* from0 = nullptr;
+  uint8_t* to0 = nullptr;
+  uint32_t skew = 0, rel = 0, owner = 0;
+  uint64_t tail = 0;
+  auto open_sge = [&](uint64_t j) {
+    const uint64_t to = sge_to[j], from = sge_from[j];
+    skew = (uint32_t)to & 15u;
+    rel = (uint32_t)(from - to) & 15u;
+    to0 = reinterpret_cast<uint8_t*>(to - skew);
+    from0 = reinterpret_cast<const uint8_t*>(from - skew - rel);
+    if constexpr (ICRC) {
+      tail = sge_tail[j];
+      owner = sge_owner[j];
+    }
+  };
+  if (c0 < c1) {
+    rocp2p_vl_seek(&cur, cstart, sge_lens, nsge, c0);
+    open_sge(cur.m);
+  }
+  uint32_t acc = 0;  // crc of this run's full chunks of SGE cur.m so far
+  uint32_t pend_f = 0, pend_m = 0;
+  const rocp2p_g16 none = {0, 0, 0, 0};
+
+  for (uint64_t c = c0; c < c1; c++) {
+    const uint64_t p0 = cur.ci * PAGE;      // of the store stream
+    const uint64_t end = skew + cur.len;    // of the SGE, likewise
+    const uint8_t* sp = from0 + p0;
+    uint8_t* dp = to0 + p0;
+    const bool full = rocp2p_b_full(skew, rel, cur.len, cur.ci);
+    // four named registers, not an array: see k_msg_engine_v
+    rocp2p_g16 v0, v1, v2, v3;
+    uint64_t done;  // store-stream bytes [.., done) are covered by acc
+    if (full) {
+      const rocp2p_g16* src = reinterpret_cast<const rocp2p_g16*>(sp);
+      if (rel == 0) {
+        v0 = src[lane];
+        v1 = src[lane + WAVE];
+        v2 = src[lane + 2 * WAVE];
+        v3 = src[lane + 3 * WAVE];
+      } else {
+        const rocp2p_g16 a0 = src[lane], a1 = src[lane + WAVE];
+        const rocp2p_g16 a2 = src[lane + 2 * WAVE], a3 = src[lane + 3 * WAVE];
+        rocp2p_g16 e = none;
+        if (lane == 0) e = src[4 * WAVE];
+        g16_realign4(a0, a1, a2, a3, e, rel, lane, v0, v1, v2, v3);
+      }
+      rocp2p_g16* dst = reinterpret_cast<rocp2p_g16*>(dp);
+      dst[lane] = v0;
+      dst[lane + WAVE] = v1;
+      dst[lane + 2 * WAVE] = v2;
+      dst[lane + 3 * WAVE] = v3;
+      if constexpr (ICRC)
+        acc = rocp2p_crc_apply(s.t.t.shift[5],
+                               rocp2p_crc_apply(s.t.t.shift[5], acc)) ^
+              icrc_chunk_full(s.t, g16_u4(v0), g16_u4(v1), g16_u4(v2),
+                              g16_u4(v3), lane);
+      done = p0 + PAGE;
+    } else {
+      const uint64_t g0 = cur.ci * ROCP2P_B_PER_CHUNK;
+      // the SGE in the source stream
+      const uint64_t sbeg = (uint64_t)skew + rel, send = end + rel;
+      auto fetch = [&](uint32_t q) {
+        uint32_t lo, hi;
+        rocp2p_b_range(sbeg, send, g0 + q, &lo, &hi);
+        return rocp2p_b_load(sp + ROCP2P_B_GRAN * q, lo, hi);
+      };
+      if (rel == 0) {
+        v0 = fetch(lane);
+        v1 = fetch(lane + WAVE);
+        v2 = fetch(lane + 2 * WAVE);
+        v3 = fetch(lane + 3 * WAVE);
+      } else {
+        const rocp2p_g16 a0 = fetch(lane), a1 = fetch(lane + WAVE);
+        const rocp2p_g16 a2 = fetch(lane + 2 * WAVE);
+        const rocp2p_g16 a3 = fetch(lane + 3 * WAVE);
+        rocp2p_g16 e = none;
+        if (lane == 0) e = fetch(4 * WAVE);
+        g16_realign4(a0, a1, a2, a3, e, rel, lane, v0, v1, v2, v3);
+      }
+      uint32_t x = 0;
+      auto put = [&](uint32_t q, const rocp2p_g16& v) {
+        uint32_t lo, hi;
+        rocp2p_b_range(skew, end, g0 + q, &lo, &hi);
+        if (lo < hi) {
+          rocp2p_b_store(dp + ROCP2P_B_GRAN * q, lo, hi, v);
+          if constexpr (ICRC)
+            x ^= rocp2p_crc_mulmod(
+                rocp2p_crc_xpow8(end - ((g0 + q) * ROCP2P_B_GRAN + hi),
+                                 c_crc.xpow8),
+                crc_granule_range(s.t.t.slice, v, lo, hi));
+        }
+      };
+      put(lane, v0);
+      put(lane + WAVE, v1);
+      put(lane + 2 * WAVE, v2);
+      put(lane + 3 * WAVE, v3);
+      if constexpr (ICRC) {
+        for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
+        // the shift is linear: the tail is applied once, to the sum
+        if (tail) x = rocp2p_crc_mulmod(crc_xpow_wave(tail, lane), x);
+        if (lane == 0) atomicXor(&out[owner], x);
+      }
+      done = p0;  // acc (if any) ends where this chunk begins
+    }
+    if constexpr (ICRC) {
+      const bool sge_end = cur.ci + 1 == cur.cpm;
+      const bool run_end = c + 1 == c1;
+      if (sge_end || run_end || !full) {
+        if (acc) {  // a zero CRC contributes nothing wherever it sits
+          const uint64_t r = end - done + tail;
+          uint32_t f = acc;
+          if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
+          if (run_end && !sge_end) {
+            pend_f = f;
+            pend_m = owner;
+          } else if (lane == 0) {
+            atomicXor(&out[owner], f);
+          }
+        }
+        acc = 0;
+      }
+    }
+    if (c + 1 < c1 && rocp2p_vl_next(&cur, cstart, sge_lens))
+      open_sge(cur.m);
+  }
+
+  if constexpr (ICRC) {
+    __syncthreads();  // the tables are dead: their first words hand off
+    vl_merge_pending(&s.t.t.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
+  }
+}
+
+// ---------------------------------------------------------------------
 // launchers
 
 static inline uint32_t stream_grid(uint64_t items, uint32_t per_block) {
@@ -1868,4 +2131,93 @@ extern "C" hipError_t rocp2p_crc32_msgs_b(const void* base,
                      (const uint8_t*)base, d_offs, d_lens,
                      (const uint64_t*)d_cstart, n, d_out);
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------
+// Scatter/gather launchers: the scan, then the engine, on one stream.
+// max_msg_bytes bounds a whole message; cut into its SGEs a message has
+// at most two chunks more per SGE than the bytes alone would give (a
+// partial first and a partial last one).  That only sizes the grid.  The
+// grid caps are msg_engine_b_launch's.
+
+static uint32_t sg_grid(uint32_t n, uint32_t nsge, uint64_t max_msg_bytes,
+                        uint64_t cap) {
+  if (!cap) cap = 1;
+  if (!max_msg_bytes) return (uint32_t)cap;
+  uint64_t bound;
+  if (__builtin_mul_overflow(rocp2p_vl_chunks(max_msg_bytes), (uint64_t)n,
+                             &bound) ||
+      __builtin_add_overflow(bound, 2 * (uint64_t)nsge, &bound))
+    return (uint32_t)cap;
+  uint64_t blocks = bound / ICRC_WAVES + (bound % ICRC_WAVES != 0);
+  return (uint32_t)(blocks > cap ? cap : blocks);  // >= 1: nsge > 0
+}
+
+template <bool GATHER>
+static hipError_t msg_engine_sg_launch(void* region, const uint64_t* d_offs,
+                                       const uint64_t* d_sge_start,
+                                       const uint64_t* d_sge_addrs,
+                                       const uint64_t* d_sge_lens, uint32_t n,
+                                       uint32_t nsge, uint64_t max_msg_bytes,
+                                       uint64_t* d_scratch, uint32_t* d_out,
+                                       uint32_t grid_cap,
+                                       hipStream_t stream) {
+  if (!d_scratch || (uintptr_t)region % 16) return hipErrorInvalidValue;
+  if (!n) return hipSuccess;
+  hipError_t e;
+  uint64_t cap = gather_grid_cap();
+  if (d_out) {
+    e = crc_tables_ready();
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+  }
+  if (!nsge) return hipSuccess;  // n messages without a byte
+  const bool small = max_msg_bytes && max_msg_bytes < PAGE;
+  if ((d_out || (GATHER && !small)) && cap > ICRC_GRID) cap = ICRC_GRID;
+  if (grid_cap && grid_cap < cap) cap = grid_cap;
+  hipLaunchKernelGGL(k_sg_scan<GATHER>, dim3(1), dim3(VL_SCAN_THREADS), 0,
+                     stream, (const uint8_t*)region, d_offs, d_sge_start,
+                     d_sge_addrs, d_sge_lens, n, nsge, d_scratch);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const rocp2p_sgl_view v = rocp2p_sgl_carve(d_scratch, nsge);
+  const uint32_t grid = sg_grid(n, nsge, max_msg_bytes, cap);
+  if (d_out)
+    hipLaunchKernelGGL(k_msg_engine_sg<true>, dim3(grid),
+                       dim3(WAVE * ICRC_WAVES), 0, stream, d_sge_lens,
+                       (const uint64_t*)v.cstart, (const uint64_t*)v.to,
+                       (const uint64_t*)v.from, (const uint64_t*)v.tail,
+                       (const uint32_t*)v.owner, nsge, d_out);
+  else
+    hipLaunchKernelGGL(k_msg_engine_sg<false>, dim3(grid),
+                       dim3(WAVE * ICRC_WAVES), 0, stream, d_sge_lens,
+                       (const uint64_t*)v.cstart, (const uint64_t*)v.to,
+                       (const uint64_t*)v.from, (const uint64_t*)v.tail,
+                       (const uint32_t*)v.owner, nsge, d_out);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rocp2p_gather_sg(
+    void* dst_base, const uint64_t* d_dst_offs, const uint64_t* d_sge_start,
+    const uint64_t* d_sge_addrs, const uint64_t* d_sge_lens, uint32_t n,
+    uint32_t nsge, uint64_t max_msg_bytes, uint64_t* d_scratch,
+    uint32_t* d_out, uint32_t grid_cap, hipStream_t stream) {
+  return msg_engine_sg_launch<true>(dst_base, d_dst_offs, d_sge_start,
+                                    d_sge_addrs, d_sge_lens, n, nsge,
+                                    max_msg_bytes, d_scratch, d_out, grid_cap,
+                                    stream);
+}
+
+extern "C" hipError_t rocp2p_scatter_sg(
+    const void* src_base, const uint64_t* d_src_offs,
+    const uint64_t* d_sge_start, const uint64_t* d_sge_addrs,
+    const uint64_t* d_sge_lens, uint32_t n, uint32_t nsge,
+    uint64_t max_msg_bytes, uint64_t* d_scratch, uint32_t* d_out,
+    uint32_t grid_cap, hipStream_t stream) {
+  // the scatter scan only ever puts the region on the side that is read
+  return msg_engine_sg_launch<false>(const_cast<void*>(src_base), d_src_offs,
+                                     d_sge_start, d_sge_addrs, d_sge_lens, n,
+                                     nsge, max_msg_bytes, d_scratch, d_out,
+                                     grid_cap, stream);
 }

@@ -57,6 +57,10 @@ def get_transport(name: str, **kw) -> Transport:
             raise NotImplementedError(
                 "verbs transport does not implement var_len=True (the "
                 "native harness posts fixed-size work requests)")
+        if kw.get("max_sge", 1) != 1:
+            raise NotImplementedError(
+                "verbs transport does not implement max_sge > 1 (the "
+                "native harness posts one SGE per work request)")
         from .verbs import VerbsTransport
 
         return VerbsTransport(**kw)

@@ -40,6 +40,19 @@ be misaligned against each other by any amount.  nbytes + skew <=
 msg_bytes holds on both sides; nbytes=None means the most that fits.
 Only nbytes bytes move; the whole rest of the slot, in front of and
 behind the message, is slack that digest_check(payload, lens) audits.
+
+`max_sge=K` with K > 1 (opt-in on top of byte_granular=True with
+staging_skew == 0, backends that support it) gives every post a
+scatter/gather list, as a work request's sg_list: `post_sg(i, sges)`
+takes up to K pairs (slot_off, nbytes), SGE k being the bytes
+[slot_off, slot_off + nbytes) of staging slot i % inflight.  The message
+is their concatenation in list order and sits at region offset
+(i % msgs_per_region) * msg_bytes + region_skew.  A write gathers the
+SGEs into that range, a read scatters the range over them (the SGEs of a
+read may not overlap: they are written).  `post(i, nbytes)` is
+`post_sg(i, [(0, nbytes)])` there, `post_many_sg(start, n, sges)` posts
+n lists at once and `digest_check_sg(payload, sges)` audits such
+traffic, the slack on the receiving side included.
 """
 from __future__ import annotations
 
@@ -51,12 +64,13 @@ class Transport(abc.ABC):
     supports_icrc = False
     supports_var_len = False
     supports_byte_granular = False
+    supports_sg_list = False
 
     def __init__(self, msg_bytes: int, region_bytes: int,
                  inflight: int | None = 8, direction: str = "write",
                  icrc: bool = False, var_len: bool = False,
                  byte_granular: bool = False, region_skew: int = 0,
-                 staging_skew: int = 0, **_):
+                 staging_skew: int = 0, max_sge: int = 1, **_):
         if icrc and not self.supports_icrc:
             raise NotImplementedError(
                 f"{self.name} transport does not implement icrc=True")
@@ -67,6 +81,11 @@ class Transport(abc.ABC):
         if var_len and not self.supports_var_len:
             raise NotImplementedError(
                 f"{self.name} transport does not implement var_len=True")
+        if int(max_sge) != max_sge or max_sge < 1:
+            raise ValueError("max_sge must be an integer >= 1")
+        if max_sge > 1 and not self.supports_sg_list:
+            raise NotImplementedError(
+                f"{self.name} transport does not implement max_sge > 1")
         if byte_granular and not var_len:
             raise ValueError("byte_granular=True needs var_len=True: only "
                              "a post that carries its own byte count can "
@@ -77,6 +96,13 @@ class Transport(abc.ABC):
                 raise ValueError(f"{what} must be an integer in [0, 16)")
             if skew and not byte_granular:
                 raise ValueError(f"{what} needs byte_granular=True")
+        if max_sge > 1 and not byte_granular:
+            raise ValueError("max_sge > 1 needs byte_granular=True: the "
+                             "SGEs of a message have any length and meet "
+                             "at any byte")
+        if max_sge > 1 and staging_skew:
+            raise ValueError("max_sge > 1 needs staging_skew == 0: every "
+                             "SGE carries its own offset into the slot")
         if max(region_skew, staging_skew) >= msg_bytes:
             raise ValueError("skew leaves no room in a slot of msg_bytes")
         if region_bytes % msg_bytes:
@@ -94,6 +120,7 @@ class Transport(abc.ABC):
         self.byte_granular = bool(byte_granular)
         self.region_skew = int(region_skew)
         self.staging_skew = int(staging_skew)
+        self.max_sge = int(max_sge)
         # the longest message a slot holds behind the larger skew
         self.max_nbytes = msg_bytes - max(self.region_skew,
                                           self.staging_skew)
@@ -173,6 +200,93 @@ class Transport(abc.ABC):
             raise ValueError(
                 f"nbytes must be a multiple of 16 in [0, {self.msg_bytes}]")
         return ln
+
+    # -- scatter/gather lists (max_sge > 1 only) -----------------------
+    def post_sg(self, i: int, sges) -> None:
+        """Enqueue message i as the concatenation of the staging-slot
+        ranges sges: a sequence of at most max_sge pairs (slot_off,
+        nbytes).  ValueError: too many SGEs, a range outside the slot, a
+        negative or non-integer value, a total that does not fit behind
+        region_skew, or (direction="read") SGEs that overlap."""
+        self._sges(sges)
+        raise NotImplementedError(
+            f"{self.name} transport does not implement post_sg")
+
+    def post_many_sg(self, start: int, n: int, sges) -> None:
+        """Enqueue messages start..start+n-1 with the lists sges: an
+        integer array of shape (n, max_sge, 2), unused entries of length
+        0.  Semantics identical to n post_sg() calls."""
+        arr = self._sges(sges, n)
+        for k in range(n):
+            self.post_sg(start + k, arr[k])
+
+    def _sges(self, sges, n: int | None = None):
+        """The lists of n posts (None: of one post, with at most max_sge
+        entries) as a validated int64 array of shape (n, max_sge, 2) —
+        (max_sge, 2) for one post —, unused entries (0, 0)."""
+        import numpy as np
+
+        if self.max_sge <= 1:
+            raise ValueError(
+                f"scatter/gather lists need a transport opened with "
+                f"max_sge > 1 (this {self.name} transport posts one range "
+                "per message)")
+        K, msg = self.max_sge, self.msg_bytes
+        try:
+            arr = np.asarray(sges)
+        except ValueError:
+            raise ValueError("sges must be pairs (slot_off, nbytes)")
+        if arr.size == 0 and n is None:
+            arr = np.zeros((0, 2), dtype=np.int64)
+        if arr.dtype.kind not in "iu":
+            raise ValueError("sges must be integers")
+        if n is None:
+            if arr.ndim != 2 or arr.shape[1] != 2:
+                raise ValueError("sges must be pairs (slot_off, nbytes)")
+            if arr.shape[0] > K:
+                raise ValueError(f"more than max_sge = {K} SGEs")
+            full = np.zeros((1, K, 2), dtype=np.int64)
+            full[0, :arr.shape[0]] = arr
+            arr = full
+        elif arr.shape != (n, K, 2):
+            raise ValueError(f"sges must have shape ({n}, {K}, 2)")
+        if arr.dtype.kind == "u" and arr.size and int(arr.max()) > msg:
+            raise ValueError("an SGE outside the slot")
+        arr = arr.astype(np.int64)
+        off, ln = arr[..., 0], arr[..., 1]
+        if (off < 0).any() or (ln < 0).any():
+            raise ValueError("negative SGE offset or length")
+        if (off + ln > msg).any():
+            raise ValueError("an SGE outside the slot of msg_bytes")
+        if (ln.sum(axis=1) + self.region_skew > msg).any():
+            raise ValueError(
+                f"a message of more than {msg - self.region_skew} bytes "
+                "(msg_bytes less region_skew)")
+        if self.direction == "read" and K > 1:
+            # the SGEs of a read are written: sorted by offset, each must
+            # end before the next one with bytes begins
+            o = np.where(ln > 0, off, msg)  # empty ones last, out of the way
+            order = np.argsort(o, axis=1, kind="stable")
+            o = np.take_along_axis(o, order, axis=1)
+            e = o + np.take_along_axis(ln, order, axis=1)
+            if (e[:, :-1] > o[:, 1:]).any():
+                raise ValueError("the SGEs of a read may not overlap")
+        return arr[0] if n is None else arr
+
+    def digest_check_sg(self, payload, sges) -> int:
+        """digest_check for scatter/gather traffic: sges has shape
+        (msgs_per_region, max_sge, 2).  Write: slot j is loaded with
+        payload[j * msg_bytes : (j + 1) * msg_bytes], the receiver must
+        hold the concatenation of the SGE ranges at its region_skew (HBM
+        digests against host zlib) and the slack in front of and behind
+        the message must still hold the known byte.  Read: the region
+        message holds the first L_j payload bytes of its slot at
+        region_skew, the slot is pre-filled with the known byte, and
+        afterwards the SGE ranges must carry the pieces in order and
+        every other slot byte must still be known.  Returns the number
+        of bad messages."""
+        raise NotImplementedError(
+            f"{self.name} transport does not implement digest_check_sg")
 
     # -- integrity plane (never timed) ---------------------------------
     @abc.abstractmethod

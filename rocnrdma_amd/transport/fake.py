@@ -16,6 +16,7 @@ class FakeTransport(Transport):
     supports_icrc = True  # zlib on the host: the sdma logic, CPU tier
     supports_var_len = True
     supports_byte_granular = True
+    supports_sg_list = True  # numpy and zlib: the sdma logic, CPU tier
     KNOWN = 0x5A  # what digest_check(payload, lens) leaves in the slack
 
     def __init__(self, msg_bytes: int, region_bytes: int, **kw):
@@ -39,6 +40,25 @@ class FakeTransport(Transport):
             dst[:] = slot
         else:
             slot[:] = dst
+
+    def post_sg(self, i: int, sges) -> None:
+        sges = self._sges(sges)
+        slot = self.staging[i % self.inflight]
+        total = int(sges[:, 1].sum())
+        off = (i % self.msgs_per_region) * self.msg_bytes + self.region_skew
+        dst = self.region[off : off + total]
+        if self.direction == "write":
+            msg = np.concatenate([slot[o : o + k] for o, k in sges])
+            if self.icrc:
+                self._digest(i, msg)
+            dst[:] = msg
+            return
+        if self.icrc:
+            self._digest(i, dst)
+        pos = 0
+        for o, k in sges:
+            slot[o : o + k] = dst[pos : pos + k]
+            pos += k
 
     def _digest(self, i: int, src) -> None:
         """The inline ICRC: digest the bytes being moved, compare with
@@ -191,6 +211,52 @@ class FakeTransport(Transport):
                 bad[i] = (got != want or
                           bool((slot[:ss] != self.KNOWN).any()) or
                           bool((slot[ss + ln:] != self.KNOWN).any()))
+            return int(bad.sum())
+        finally:
+            if self.icrc:
+                self._inline = None
+
+    def digest_check_sg(self, payload, sges) -> int:
+        pay = self._payload_bytes(payload)
+        n, msg, rs = self.msgs_per_region, self.msg_bytes, self.region_skew
+        sges = self._sges(sges, n)
+        lens = sges[:, :, 1].sum(axis=1)
+        write = self.direction == "write"
+        if self.icrc:
+            self._expected = None
+            self._inline = []
+        try:
+            bad = np.zeros(n, dtype=bool)
+            if write:
+                self.region[:] = self.KNOWN
+            else:  # the first L_j payload bytes of the slot, at the skew
+                self.region[:] = pay
+                for i in range(n):
+                    self.region[i * msg + rs : i * msg + rs + lens[i]] = \
+                        pay[i * msg : i * msg + lens[i]]
+            for i in range(n):
+                slot = self.staging[i % self.inflight]
+                slot[:] = pay[i * msg : (i + 1) * msg] if write else self.KNOWN
+                self.post_sg(i, sges[i])
+                self.flush()
+                ln = int(lens[i])
+                pieces = np.concatenate([slot[o : o + k] for o, k in sges[i]])
+                host = zlib.crc32(pieces.tobytes())
+                if write:
+                    there = self.region[i * msg : (i + 1) * msg]
+                    got = (self._inline[i] if self.icrc else
+                           zlib.crc32(there[rs : rs + ln].tobytes()))
+                    bad[i] = (got != host or
+                              bool((there[:rs] != self.KNOWN).any()) or
+                              bool((there[rs + ln:] != self.KNOWN).any()))
+                else:
+                    want = (self._inline[i] if self.icrc else
+                            zlib.crc32(pay[i * msg : i * msg + ln].tobytes()))
+                    rest = np.ones(msg, dtype=bool)
+                    for o, k in sges[i]:
+                        rest[o : o + k] = False
+                    bad[i] = (host != want or
+                              bool((slot[rest] != self.KNOWN).any()))
             return int(bad.sum())
         finally:
             if self.icrc:

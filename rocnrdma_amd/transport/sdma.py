@@ -34,6 +34,13 @@ byte_granular=True (on top of var_len) retires the same ring with
 ops.gather_bytes_/scatter_bytes_: any byte count, and region_skew /
 staging_skew move every region offset and staging address of the ring
 by a constant, so the rows stay what they were.
+
+max_sge=K > 1 (on top of byte_granular, staging_skew == 0) gives every
+WQE a fixed K SGE fields (address, length) next to its region offset, as
+a hardware WQE has: a list with fewer SGEs leaves the others at length
+0, so the CSR row starts are the constant arange(inflight + 1) * K, built
+once on the device.  flush() retires the ring with one
+ops.gather_sg_/scatter_sg_ launch (crc=icrc) on the flush stream.
 """
 from __future__ import annotations
 
@@ -58,6 +65,7 @@ class SdmaTransport(Transport):
     supports_icrc = True
     supports_var_len = True
     supports_byte_granular = True
+    supports_sg_list = True
 
     def __init__(self, msg_bytes: int, region_bytes: int, device=None,
                  num_streams: int = 2, engine: str = "auto",
@@ -78,6 +86,12 @@ class SdmaTransport(Transport):
                 "var_len=True needs the kernel engine: only its WQEs "
                 "carry a length; the stream engine (explicit, or picked "
                 "by auto for slots of 8 MiB and up) copies whole slots")
+        if kw.get("max_sge", 1) != 1 and engine != "kernel":
+            raise ValueError(
+                "max_sge > 1 needs the kernel engine: only its WQEs carry "
+                "a scatter/gather list; the stream engine (explicit, or "
+                "picked by auto for slots of 8 MiB and up) copies whole "
+                "slots")
         if inflight in (None, 0):
             if engine == "kernel":
                 inflight = max(8, min(region_bytes // msg_bytes,
@@ -119,6 +133,19 @@ class SdmaTransport(Transport):
                                          dtype=torch.int64,
                                          device=self.device)
             self._pending = 0
+            if self.max_sge > 1:
+                # the SGE fields of the ring: [address | length][WQE][SGE]
+                K = self.max_sge
+                self._sg_pin = torch.zeros((2, self.inflight, K),
+                                           dtype=torch.int64, pin_memory=True)
+                self._sg_np = self._sg_pin.numpy()
+                self._sg_dev = torch.empty((2, self.inflight * K),
+                                           dtype=torch.int64,
+                                           device=self.device)
+                self._sg_start = torch.arange(
+                    self.inflight + 1, dtype=torch.int64,
+                    device=self.device) * K
+                torch.cuda.synchronize(self.device)
         if self.icrc:
             self._stamped = False
             self._exp_slot_np = None  # write: int32-wrapped CRC per slot
@@ -132,6 +159,8 @@ class SdmaTransport(Transport):
 
     # -- data plane ----------------------------------------------------
     def post(self, i: int, nbytes: int | None = None) -> None:
+        if self.max_sge > 1:
+            return self.post_sg(i, [(0, self._len1(nbytes))])
         if nbytes is not None or self.var_len:
             nbytes = self._len1(nbytes)
         off = (i % self.msgs_per_region) * self.msg_bytes + self.region_skew
@@ -166,6 +195,10 @@ class SdmaTransport(Transport):
             return super().post_many(start, n, nbytes)
         import numpy as np
 
+        if self.max_sge > 1:  # one SGE each: the slot's first nbytes
+            sges = np.zeros((n, self.max_sge, 2), dtype=np.int64)
+            sges[:, 0, 1] = self._lens(nbytes, n)
+            return self.post_many_sg(start, n, sges)
         lens = None
         if nbytes is not None or self.var_len:
             lens = self._lens(nbytes, n)  # one vectorized check
@@ -193,6 +226,34 @@ class SdmaTransport(Transport):
             self._pending = k + take
             done += take
 
+    def post_sg(self, i: int, sges) -> None:
+        self.post_many_sg(i, 1, self._sges(sges)[None])
+
+    def post_many_sg(self, start: int, n: int, sges) -> None:
+        """Vectorized WQE writes for scatter/gather lists: the region
+        offset row as in post_many, and the K SGE fields per WQE."""
+        import numpy as np
+
+        sges = self._sges(sges, n)  # one vectorized check
+        done = 0
+        while done < n:
+            if self._pending >= self.inflight:
+                self.flush()
+            k = self._pending
+            take = min(n - done, self.inflight - k)
+            idx = np.arange(start + done, start + done + take,
+                            dtype=np.int64)
+            self._desc_np[ROW_OFF, k:k + take] = \
+                (idx % self.msgs_per_region) * self.msg_bytes + \
+                self.region_skew
+            part = sges[done:done + take]
+            self._sg_np[0, k:k + take] = \
+                self._slot_addr_np[idx % self.inflight][:, None] + \
+                part[:, :, 0]
+            self._sg_np[1, k:k + take] = part[:, :, 1]
+            self._pending = k + take
+            done += take
+
     def flush(self) -> None:
         if self.engine == "kernel":
             n = self._pending
@@ -204,7 +265,9 @@ class SdmaTransport(Transport):
                 with torch.cuda.stream(stream):
                     self._desc_dev[:, :n].copy_(self._desc_pin[:, :n],
                                                 non_blocking=True)
-                    if self.var_len:
+                    if self.max_sge > 1:
+                        self._flush_sg(n)
+                    elif self.var_len:
                         self._flush_var_len(n)
                     elif self.icrc:
                         self._flush_icrc(n)
@@ -254,6 +317,25 @@ class SdmaTransport(Transport):
                      max_msg_bytes=self.msg_bytes, crc=self.icrc)
         if self.icrc:
             self._last_digests = dig
+
+    def _flush_sg(self, n: int) -> None:
+        """One scatter/gather engine launch for the ring, on the current
+        (flush) stream; with icrc the digests of the batch are kept."""
+        from .. import ops
+
+        nsge = n * self.max_sge
+        self._sg_dev[:, :nsge].copy_(
+            self._sg_pin.view(2, -1)[:, :nsge], non_blocking=True)
+        engine = (ops.gather_sg_ if self.direction == "write"
+                  else ops.scatter_sg_)
+        dig = engine(self.region, self._desc_dev[ROW_OFF, :n],
+                     self._sg_start[:n + 1], self._sg_dev[0, :nsge],
+                     self._sg_dev[1, :nsge], max_msg_bytes=self.msg_bytes,
+                     crc=self.icrc)
+        if self.icrc:
+            self._last_digests = dig
+        # (the pinned SGE fields may be rewritten once flush() has
+        # synchronised, as the rest of the ring)
 
     def stamp(self) -> None:
         if not self.icrc or self.var_len:
@@ -486,6 +568,91 @@ class SdmaTransport(Transport):
             bad |= slack.cpu().numpy().view(np.uint32) != want
             if rs:
                 front = crc_v(self.region, d_offs - rs,
+                              torch.full_like(d_lens, rs), max_msg_bytes=16)
+                bad |= (front.cpu().numpy().view(np.uint32)
+                        != zlib.crc32(bytes([_KNOWN]) * rs))
+        bad |= hbm.cpu().numpy().view(np.uint32) != host
+        return int(bad.sum())
+
+    def digest_check_sg(self, payload, sges) -> int:
+        """digest_check for scatter/gather traffic (see the base class).
+        HBM-side digests: the fused engine's (icrc) or one
+        crc32_messages_bytes launch over the region ranges; host side:
+        zlib over the concatenated SGE ranges of the slot.  The slack in
+        HBM is digested as in digest_check(payload, lens), the slack of a
+        slot is inspected with numpy."""
+        import zlib
+
+        import numpy as np
+
+        from .. import ops
+
+        pay = self._payload_bytes(payload)
+        pay_t = torch.from_numpy(pay)
+        n, msg, rs = self.msgs_per_region, self.msg_bytes, self.region_skew
+        sges = self._sges(sges, n)
+        lens = sges[:, :, 1].sum(axis=1)
+        write = self.direction == "write"
+        if self.icrc:
+            self._stamped = False
+        d_offs = torch.from_numpy(
+            np.arange(n, dtype=np.int64) * msg + rs).to(self.device)
+        d_lens = torch.from_numpy(lens).to(self.device)
+        if write:
+            self.region.fill_(_KNOWN)
+        else:  # the first L_j payload bytes of the slot, at the skew
+            reg = pay.copy()
+            for j in range(n):
+                reg[j * msg + rs:j * msg + rs + lens[j]] = \
+                    pay[j * msg:j * msg + lens[j]]
+            self.region.copy_(torch.from_numpy(reg))
+        torch.cuda.synchronize(self.device)
+
+        def pieces(slot, j):
+            return np.concatenate([slot[o:o + k] for o, k in sges[j]])
+
+        host = np.empty(n, dtype=np.uint32)
+        bad = np.zeros(n, dtype=bool)
+        inline = []
+        i = 0
+        while i < n:
+            burst = min(self.inflight, n - i)
+            if write:
+                for j in range(i, i + burst):
+                    slot = self.staging[j % self.inflight]
+                    slot.copy_(pay_t[j * msg:(j + 1) * msg])
+                    host[j] = zlib.crc32(pieces(slot.numpy(), j))
+            else:
+                self.staging_flat[:burst * msg].fill_(_KNOWN)
+            self.post_many_sg(i, burst, sges[i:i + burst])
+            self.flush()  # slots reused next burst: must complete
+            if self.icrc:
+                inline.append(self._last_digests)
+            if not write:
+                for j in range(i, i + burst):
+                    slot = self.staging[j % self.inflight].numpy()
+                    host[j] = zlib.crc32(pieces(slot, j))
+                    rest = np.ones(msg, dtype=bool)
+                    for o, k in sges[j]:
+                        rest[o:o + k] = False
+                    bad[j] = bool((slot[rest] != _KNOWN).any())
+            i += burst
+        crc_b = ops.crc32_messages_bytes
+        if self.icrc:
+            hbm = torch.cat(inline)
+        else:
+            hbm = crc_b(self.region, d_offs, d_lens, max_msg_bytes=msg)
+        if write:
+            behind = msg - rs - lens
+            slack = crc_b(self.region, d_offs + d_lens, msg - rs - d_lens,
+                          max_msg_bytes=msg)
+            known = {int(k): zlib.crc32(bytes([_KNOWN]) * int(k))
+                     for k in np.unique(behind)}
+            want = np.array([known[int(k)] for k in behind],
+                            dtype=np.uint32)
+            bad |= slack.cpu().numpy().view(np.uint32) != want
+            if rs:
+                front = crc_b(self.region, d_offs - rs,
                               torch.full_like(d_lens, rs), max_msg_bytes=16)
                 bad |= (front.cpu().numpy().view(np.uint32)
                         != zlib.crc32(bytes([_KNOWN]) * rs))
