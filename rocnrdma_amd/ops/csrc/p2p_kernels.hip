@@ -410,92 +410,130 @@ __device__ __forceinline__ uint32_t crc_bytes64(const rocp2p_crc_tab256* t,
   return crc ^ 0xFFFFFFFFu;
 }
 
-// One wave per run of `run` consecutive chunks; CRC_DIGEST_WAVES waves
-// per workgroup share one copy of the tables.
-// Message m starts at base + (offs ? offs[m] : m * msg_bytes); cpm =
-// chunks per message = ceil(msg_bytes / 4096); total = n * cpm.
-#define CRC_DIGEST_WAVES 16u
-__global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
-    const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
-    uint64_t msg_bytes, uint64_t cpm, uint64_t total, uint64_t run,
-    uint32_t* __restrict__ out) {
-  __shared__ crc_lds s;
-  crc_stage_tables(s);
+// This lane's share of a partial chunk's digest: the chunk's first
+// `valid` (1..4095) bytes, seg = this lane's 64-byte segment of it.
+__device__ __forceinline__ uint32_t crc_chunk_partial(const crc_lds& s,
+                                                      const uint8_t* seg,
+                                                      uint32_t valid,
+                                                      uint32_t lane) {
+  const uint32_t beg = lane * SEG;
+  const uint32_t nb = valid > beg ? min(valid - beg, SEG) : 0u;
+  uint32_t w[16];
+  crc_load_partial(seg, nb, w);
+  if (!nb) return 0;
+  return rocp2p_crc_mulmod(rocp2p_crc_xpow8(valid - (beg + nb), c_crc.xpow8),
+                           crc_bytes64(s.slice, w, nb));
+}
 
-  const uint32_t lane = threadIdx.x & (WAVE - 1);
-  const uint32_t wv = threadIdx.x / WAVE, nwv = blockDim.x / WAVE;
-  const uint64_t wave = (uint64_t)blockIdx.x * nwv + wv;
-  uint64_t c0 = wave * run;
-  if (c0 > total) c0 = total;  // idle wave: empty run, still joins the merge
-  const uint64_t c1 = (total - c0 < run) ? total : c0 + run;
+// ---------------------------------------------------------------------
+// The run walk: the shape every digest kernel and every message engine
+// below has, and the pieces of it that k_crc32_msgs, k_msg_engine_v and
+// k_crc32_msgs_b share.  (k_msg_engine_crc, k_crc32_msgs_v,
+// k_msg_engine_b and k_msg_engine_sg keep their own bodies: on the
+// shared ones they measured slower, docs/PERF.md §8.)
+// The work items of a batch (messages, or SGEs) are cut
+// into 4 KiB chunks, numbered item-major; a wave owns the contiguous
+// chunks [c0, c1), finds the item of c0 once and then only steps
+// forward.  A kernel supplies
+//  - how the run is sized (wave_run::split: from the launcher, or from
+//    the chunk total a scan kernel left in device memory),
+//  - how the cursor moves (uni_batch, vl_batch: seek and next),
+//  - what opening an item means and what one chunk does,
+// and, when it digests, carries a crc_run through the walk: acc over the
+// full chunks, flush when the item or the run ends, the workgroup merge
+// of the shares of runs that ended inside a message.
 
-  uint64_t m = 0, ci = 0;
-  const uint8_t* mp = base;
-  if (c0 < c1) {
-    m = c0 / cpm;
-    ci = c0 - m * cpm;
-    mp = base + (offs ? offs[m] : m * msg_bytes);
+struct wave_run {
+  uint32_t lane, wv, nwv;  // wv: this wave in the workgroup, of nwv
+  uint64_t wave, nwaves;   // ... and in the grid
+  uint64_t c0, c1;
+
+  // The launcher chose the run length (run > 0).  Waves past the end get
+  // an empty run and still join the merge.
+  __device__ __forceinline__ void split(uint64_t total, uint64_t run) {
+    c0 = wave * run;
+    if (c0 > total) c0 = total;
+    c1 = (total - c0 < run) ? total : c0 + run;
   }
-  uint32_t acc = 0;  // crc of this run's full chunks of message m so far
-  // contribution of a run that ends inside a message: merged with the
-  // workgroup's other waves below (0 contributes nothing)
-  uint32_t pend_f = 0, pend_m = 0;
-
-  for (uint64_t c = c0; c < c1; c++) {
-    const uint64_t pos = ci * PAGE;
-    const uint64_t left = msg_bytes - pos;  // > 0
-    const uint8_t* seg = mp + pos + lane * SEG;
-    uint64_t done;  // message bytes [.., done) are covered by acc
-    if (left >= PAGE) {
-      acc = rocp2p_crc_apply(s.shift[5], rocp2p_crc_apply(s.shift[5], acc)) ^
-            crc_page(seg, lane, s);
-      done = pos + PAGE;
-    } else {
-      const uint32_t valid = (uint32_t)left;  // 1..4095
-      const uint32_t beg = lane * SEG;
-      const uint32_t nb = valid > beg ? min(valid - beg, SEG) : 0u;
-      uint32_t w[16];
-      crc_load_partial(seg, nb, w);
-      uint32_t x = 0;
-      if (nb)
-        x = rocp2p_crc_mulmod(
-            rocp2p_crc_xpow8(valid - (beg + nb), c_crc.xpow8),
-            crc_bytes64(s.slice, w, nb));
-      for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
-      if (lane == 0) atomicXor(&out[m], x);
-      done = pos;  // acc (if any) still has `valid` bytes after it
-    }
-    const bool msg_end = ci + 1 == cpm;
-    if (msg_end || c + 1 == c1) {
-      if (acc) {  // a zero CRC contributes nothing wherever it sits
-        const uint64_t r = msg_bytes - done;
-        uint32_t f = acc;
-        if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
-        if (msg_end) {
-          if (lane == 0) atomicXor(&out[m], f);
-        } else {
-          pend_f = f;
-          pend_m = (uint32_t)m;
-        }
-      }
-      acc = 0;
-    }
-    if (msg_end) {
-      m++;
-      ci = 0;
-      if (c + 1 < c1) mp = base + (offs ? offs[m] : m * msg_bytes);
-    } else {
-      ci++;
-    }
+  // Equal runs over a total only the device knows.
+  __device__ __forceinline__ void split(uint64_t total) {
+    rocp2p_vl_run(total, nwaves, wave, &c0, &c1);
   }
+};
 
-  // Adjacent waves own adjacent runs, so in a long message the whole
-  // workgroup's pending shares target one digest: XOR them here and
-  // issue one atomic instead of one per wave (same-line atomics
-  // serialize in L2).  The tables are dead after the barrier; their
-  // first words carry the hand-off.
-  __syncthreads();
-  uint32_t* s_pend = &s.slice[0][0];
+// The wave index is made provably uniform, so the cursor and the
+// descriptors it loads live in SGPRs.  nwv = blockDim.x / WAVE, which
+// the kernel itself has to read: only in a __global__ function does the
+// compiler fold the block size to one scalar load of a kernel argument;
+// read in a helper it is a vector load that every wave waits for before
+// it knows its run.
+__device__ __forceinline__ wave_run wave_run_open(uint32_t nwv) {
+  wave_run w;
+  w.lane = threadIdx.x & (WAVE - 1);
+  w.wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+  w.nwv = nwv;
+  w.wave = (uint64_t)blockIdx.x * nwv + w.wv;
+  w.nwaves = (uint64_t)gridDim.x * nwv;
+  w.c0 = w.c1 = 0;
+  return w;
+}
+
+// Every item has msg_bytes bytes and so cpm = ceil(msg_bytes / 4096)
+// chunks: the cursor is a divide and a wrap.
+struct uni_batch {
+  uint64_t msg_bytes, cpm;
+  __device__ __forceinline__ void seek(rocp2p_vl_cursor* cur,
+                                       uint64_t c) const {
+    cur->m = c / cpm;
+    cur->ci = c - cur->m * cpm;
+    cur->cpm = cpm;
+    cur->len = msg_bytes;
+  }
+  __device__ __forceinline__ bool next(rocp2p_vl_cursor* cur) const {
+    if (++cur->ci < cpm) return false;
+    cur->m++;
+    cur->ci = 0;
+    return true;
+  }
+};
+
+// Items carry their own lengths; cstart holds the chunk prefix sums a
+// scan kernel wrote (p2p_varlen.h).
+struct vl_batch {
+  const uint64_t* cstart;
+  const uint64_t* lens;
+  uint64_t n;
+  __device__ __forceinline__ void seek(rocp2p_vl_cursor* cur,
+                                       uint64_t c) const {
+    rocp2p_vl_seek(cur, cstart, lens, n, c);
+  }
+  __device__ __forceinline__ bool next(rocp2p_vl_cursor* cur) const {
+    return rocp2p_vl_next(cur, cstart, lens);
+  }
+};
+
+// XOR-reduce x over the wave, shift the sum by `tail` more bytes (the
+// shift is linear: applied once, to the sum) and XOR it into *digest.
+__device__ __forceinline__ void crc_wave_emit(uint32_t x, uint64_t tail,
+                                              uint32_t lane,
+                                              uint32_t* digest) {
+  for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
+  if (tail) x = rocp2p_crc_mulmod(crc_xpow_wave(tail, lane), x);
+  if (lane == 0) atomicXor(digest, x);
+}
+
+// Merge the pending shares (runs that ended inside a message) of a
+// workgroup's waves.  Adjacent waves own adjacent runs, so in a long
+// message the whole workgroup's pending shares target one digest and
+// equal targets are adjacent: XOR them and issue one atomic instead of
+// one per wave (same-line atomics serialize in L2).  s_pend: 2 * nwv
+// words of LDS that are dead by now (the tables' first words); the
+// caller has passed the barrier that says so.
+__device__ __forceinline__ void crc_merge_pending(uint32_t* s_pend,
+                                                  uint32_t lane, uint32_t wv,
+                                                  uint32_t nwv, uint32_t pend_f,
+                                                  uint32_t pend_m,
+                                                  uint32_t* __restrict__ out) {
   if (lane == 0) {
     s_pend[2 * wv] = pend_f;
     s_pend[2 * wv + 1] = pend_m;
@@ -515,6 +553,107 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
   }
 }
 
+// The CRC a wave carries through its run.
+struct crc_run {
+  uint32_t acc = 0;  // crc of this run's full chunks of the item so far
+  // contribution of a run that ends inside a message: merged with the
+  // workgroup's other waves (0 contributes nothing)
+  uint32_t pend_f = 0, pend_m = 0;
+
+  // acc = crc(chunks so far || one more 4 KiB chunk)
+  __device__ __forceinline__ void full_chunk(const crc_lds& t, uint32_t crc) {
+    acc = rocp2p_crc_apply(t.shift[5], rocp2p_crc_apply(t.shift[5], acc)) ^
+          crc;
+  }
+
+  // After every chunk.  acc leaves the wave when the item ends, when the
+  // run ends, or when the chunk just done was not a full one (!full: its
+  // bytes went straight to the digest and acc does not cover them).
+  // `behind`: the message bytes after those acc covers; `key`: the
+  // digest they belong to.  A run that ends inside an item parks its
+  // share for merge().
+  __device__ __forceinline__ void flush(bool item_end, bool run_end, bool full,
+                                        uint64_t behind, uint32_t key,
+                                        uint32_t lane,
+                                        uint32_t* __restrict__ out) {
+    if (item_end || run_end || !full) {
+      if (acc) {  // a zero CRC contributes nothing wherever it sits
+        uint32_t f = acc;
+        if (behind) f = rocp2p_crc_mulmod(crc_xpow_wave(behind, lane), acc);
+        if (run_end && !item_end) {
+          pend_f = f;
+          pend_m = key;
+        } else if (lane == 0) {
+          atomicXor(&out[key], f);
+        }
+      }
+      acc = 0;
+    }
+  }
+
+  // After the walk, by every wave of the workgroup: the barrier that
+  // says the tables are dead, then the merge.
+  __device__ __forceinline__ void merge(uint32_t* s_pend, const wave_run& w,
+                                        uint32_t* __restrict__ out) const {
+    __syncthreads();
+    crc_merge_pending(s_pend, w.lane, w.wv, w.nwv, pend_f, pend_m, out);
+  }
+};
+
+// The digest walk over messages cut from their own start: message m is
+// the cur.len bytes at where(m).
+template <typename Batch, typename Where>
+__device__ __forceinline__ void crc32_msgs_walk(crc_lds& s, const wave_run& w,
+                                                const Batch& batch,
+                                                Where where,
+                                                uint32_t* __restrict__ out) {
+  crc_run crc;
+  if (w.c0 < w.c1) {
+    rocp2p_vl_cursor cur;
+    batch.seek(&cur, w.c0);
+    const uint8_t* mp = where(cur.m);
+    for (uint64_t c = w.c0; c < w.c1; c++) {
+      const uint64_t pos = cur.ci * PAGE;
+      const uint64_t left = cur.len - pos;  // > 0
+      const uint8_t* seg = mp + pos + w.lane * SEG;
+      uint64_t done;  // message bytes [.., done) are covered by acc
+      if (left >= PAGE) {
+        crc.full_chunk(s, crc_page(seg, w.lane, s));
+        done = pos + PAGE;
+      } else {
+        crc_wave_emit(crc_chunk_partial(s, seg, (uint32_t)left, w.lane), 0,
+                      w.lane, &out[cur.m]);
+        done = pos;  // acc (if any) still has `left` bytes after it
+      }
+      // a partial chunk is a message's last: the general rule's !full
+      // never adds anything here
+      crc.flush(cur.ci + 1 == cur.cpm, c + 1 == w.c1, true, cur.len - done,
+                (uint32_t)cur.m, w.lane, out);
+      if (c + 1 < w.c1 && batch.next(&cur)) mp = where(cur.m);
+    }
+  }
+  crc.merge(&s.slice[0][0], w, out);
+}
+
+// One wave per run of `run` consecutive chunks; CRC_DIGEST_WAVES waves
+// per workgroup share one copy of the tables.
+// Message m starts at base + (offs ? offs[m] : m * msg_bytes); cpm =
+// chunks per message = ceil(msg_bytes / 4096); total = n * cpm.
+#define CRC_DIGEST_WAVES 16u
+__global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
+    const uint8_t* __restrict__ base, const uint64_t* __restrict__ offs,
+    uint64_t msg_bytes, uint64_t cpm, uint64_t total, uint64_t run,
+    uint32_t* __restrict__ out) {
+  __shared__ crc_lds s;
+  crc_stage_tables(s);
+  wave_run w = wave_run_open(blockDim.x / WAVE);
+  w.split(total, run);
+  crc32_msgs_walk(
+      s, w, uni_batch{msg_bytes, cpm},
+      [&](uint64_t m) { return base + (offs ? offs[m] : m * msg_bytes); },
+      out);
+}
+
 // ---------------------------------------------------------------------
 // Message engine with inline ICRC: moves the batch like k_msg_engine and
 // digests every message from the registers the bytes pass through, the
@@ -523,11 +662,12 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs(
 // in HBM is crc32_messages' business.
 //
 // Work split, running CRC, end-of-run shift and the workgroup merge are
-// k_crc32_msgs' (above).  What differs is the chunk layout: a lane of a
-// full 4 KiB chunk holds the 16-byte pieces l, l+64, l+128, l+192, so
-// every wave load/store is one contiguous 1 KiB access — the shape the
-// plain engine's PCIe rate was measured with (crc_page's 64 B per lane
-// would make each wave load 64 separate 16-byte PCIe reads).  Piece
+// the run walk's (above).  What differs from the digest kernels is the
+// chunk layout: a lane of a full 4 KiB chunk holds the 16-byte pieces
+// l, l+64, l+128, l+192, so every wave load/store is one contiguous
+// 1 KiB access — the shape the plain engine's PCIe rate was measured
+// with (crc_page's 64 B per lane would make each wave load 64 separate
+// 16-byte PCIe reads).  Piece
 // q = 64u + l has 1024(3-u) + 16(63-l) bytes of the chunk after it, and
 // shifts commute: a lane Horner-folds its four piece CRCs with the
 // 1 KiB operator (shift[4]), then one log tree over the lanes with the
@@ -542,6 +682,13 @@ struct icrc_lds {
   uint32_t shift16[2][4][256];
 };
 
+// crc_stage_tables plus the 16- and 32-byte operators
+__device__ __forceinline__ void icrc_stage_tables(icrc_lds& s) {
+  for (uint32_t i = threadIdx.x; i < 2 * 4 * 256; i += blockDim.x)
+    (&s.shift16[0][0][0])[i] = (&c_crc.shift16[0][0][0])[i];
+  crc_stage_tables(s.t);
+}
+
 // zlib crc32 of one 16-byte piece
 __device__ __forceinline__ uint32_t crc_piece16(const rocp2p_crc_tab256* t,
                                                 const uint4& v) {
@@ -549,7 +696,112 @@ __device__ __forceinline__ uint32_t crc_piece16(const rocp2p_crc_tab256* t,
   return rocp2p_crc_step8(t, crc, v.z, v.w) ^ 0xFFFFFFFFu;
 }
 
+// zlib crc32 of a full 4 KiB chunk held the engine's way (lane l: pieces
+// l, l+64, l+128, l+192), in every lane.
+__device__ __forceinline__ uint32_t icrc_chunk_full(const icrc_lds& s,
+                                                    const uint4& v0,
+                                                    const uint4& v1,
+                                                    const uint4& v2,
+                                                    const uint4& v3,
+                                                    uint32_t lane) {
+  uint32_t crc = crc_piece16(s.t.slice, v0);
+  crc = rocp2p_crc_apply(s.t.shift[4], crc) ^ crc_piece16(s.t.slice, v1);
+  crc = rocp2p_crc_apply(s.t.shift[4], crc) ^ crc_piece16(s.t.slice, v2);
+  crc = rocp2p_crc_apply(s.t.shift[4], crc) ^ crc_piece16(s.t.slice, v3);
+  // lane tree: level k merges adjacent spans of 16 B << k
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    uint32_t partner = __shfl_xor(crc, 1u << k, WAVE);
+    bool is_left = ((lane >> k) & 1u) == 0;
+    uint32_t cl = is_left ? crc : partner;
+    uint32_t cr = is_left ? partner : crc;
+    crc = rocp2p_crc_apply(k < 2 ? s.shift16[k] : s.t.shift[k - 2], cl) ^ cr;
+  }
+  return crc;
+}
+
+// The plain form keeps nothing in LDS.
+template <bool ICRC>
+struct vl_engine_lds {};
+template <>
+struct vl_engine_lds<true> {
+  icrc_lds t;
+};
+
+// The message engine over lengths that are multiples of 16, with (ICRC)
+// or without the inline digest: one walk, so both forms move bytes the
+// same way — 1 KiB-contiguous wave accesses, lane l holding pieces l,
+// l+64, l+128, l+192 of a chunk.  Without ICRC no table is staged and
+// no CRC work is done.
 #define ICRC_WAVES 4u
+template <bool GATHER, bool ICRC, typename Batch>
+__device__ __forceinline__ void msg_engine_walk(
+    vl_engine_lds<ICRC>& s, const wave_run& w, const Batch& batch,
+    uint8_t* __restrict__ region, const uint64_t* __restrict__ offs,
+    const uint64_t* __restrict__ addrs, uint32_t* __restrict__ out) {
+  const uint32_t lane = w.lane;
+  crc_run crc;
+  if (w.c0 < w.c1) {
+    rocp2p_vl_cursor cur;
+    // this message on the side that is read and on the side that is written
+    const uint8_t* from = nullptr;
+    uint8_t* to = nullptr;
+    auto open_msg = [&](uint64_t msg) {
+      uint8_t* inside = region + offs[msg];
+      uint8_t* outside = reinterpret_cast<uint8_t*>(addrs[msg]);
+      from = GATHER ? outside : inside;
+      to = GATHER ? inside : outside;
+    };
+    batch.seek(&cur, w.c0);
+    open_msg(cur.m);
+
+    for (uint64_t c = w.c0; c < w.c1; c++) {
+      const uint64_t pos = cur.ci * PAGE;
+      const uint64_t left = cur.len - pos;  // > 0, a multiple of 16
+      const uint4* src = reinterpret_cast<const uint4*>(from + pos);
+      uint4* dst = reinterpret_cast<uint4*>(to + pos);
+      uint64_t done;  // message bytes [.., done) are covered by acc
+      if (left >= PAGE) {
+        // four named registers, not an array: the plain form would
+        // otherwise get the array promoted to LDS
+        const uint4 v0 = src[lane], v1 = src[lane + WAVE];
+        const uint4 v2 = src[lane + 2 * WAVE], v3 = src[lane + 3 * WAVE];
+        dst[lane] = v0;
+        dst[lane + WAVE] = v1;
+        dst[lane + 2 * WAVE] = v2;
+        dst[lane + 3 * WAVE] = v3;
+        if constexpr (ICRC)
+          crc.full_chunk(s.t.t, icrc_chunk_full(s.t, v0, v1, v2, v3, lane));
+        done = pos + PAGE;
+      } else {
+        const uint32_t valid = (uint32_t)left;  // 16..4080
+        const uint32_t nvec = valid / 16;
+        uint32_t x = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < 4; u++) {
+          const uint32_t q = lane + WAVE * u;
+          if (q < nvec) {
+            uint4 v = src[q];
+            dst[q] = v;
+            if constexpr (ICRC)
+              x ^= rocp2p_crc_mulmod(
+                  rocp2p_crc_xpow8(valid - 16 * (q + 1), c_crc.xpow8),
+                  crc_piece16(s.t.t.slice, v));
+          }
+        }
+        if constexpr (ICRC) crc_wave_emit(x, 0, lane, &out[cur.m]);
+        done = pos;  // acc (if any) still has `valid` bytes after it
+      }
+      if constexpr (ICRC)
+        crc.flush(cur.ci + 1 == cur.cpm, c + 1 == w.c1, true, cur.len - done,
+                  (uint32_t)cur.m, lane, out);
+      if (c + 1 < w.c1 && batch.next(&cur)) open_msg(cur.m);
+    }
+  }
+  if constexpr (ICRC) crc.merge(&s.t.t.slice[0][0], w, out);
+}
+
+// Uniform msg_bytes per batch; run length from the launcher.
 template <bool GATHER>
 __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_crc(
     uint8_t* __restrict__ region, const uint64_t* __restrict__ offs,
@@ -658,26 +910,8 @@ __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_crc(
     }
   }
 
-  // merge the workgroup's pending shares, as k_crc32_msgs does
-  __syncthreads();
-  uint32_t* s_pend = &s.t.slice[0][0];
-  if (lane == 0) {
-    s_pend[2 * wv] = pend_f;
-    s_pend[2 * wv + 1] = pend_m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t f = s_pend[0], fm = s_pend[1];
-    for (uint32_t w = 1; w < nwv; w++) {
-      if (s_pend[2 * w + 1] != fm) {
-        if (f) atomicXor(&out[fm], f);
-        f = 0;
-        fm = s_pend[2 * w + 1];
-      }
-      f ^= s_pend[2 * w];
-    }
-    if (f) atomicXor(&out[fm], f);
-  }
+  __syncthreads();  // the tables are dead: their first words hand off
+  crc_merge_pending(&s.t.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
 }
 
 // ---------------------------------------------------------------------
@@ -697,109 +931,66 @@ __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_crc(
 // cost: a run boundary may fall anywhere, inside a big message or after
 // any number of tiny ones.
 
-// One workgroup of 16 waves; wave w owns a contiguous segment of the
-// messages (a whole number of 64-message tiles, so any n fits and every
-// tile is one coalesced 512-byte access).  Pass 1 sums the segment, one
-// barrier hands the 16 sums over, pass 2 walks the segment tile by tile
-// with a wave scan and a running carry — no barrier inside either loop.
+// A scan of value(0 .. count - 1) by one workgroup of 16 waves; wave w
+// owns a contiguous segment of the items (a whole number of 64-item
+// tiles, so any count fits and every tile is one coalesced access).
+// Pass 1 sums the segment, one barrier hands the 16 sums over, pass 2
+// walks the segment tile by tile with a wave scan and a running carry —
+// no barrier inside either loop.  PARK keeps the values in out between
+// the passes so that value() runs once per item (the same lane owns an
+// item in both passes); a value() that is two loads and a shift is
+// cheaper run twice.  Sums (MAX false) are exclusive, out[0 .. count]
+// with the total last; running maxima (MAX true) are inclusive,
+// out[0 .. count).  A PARK scan ends with a barrier — out is complete
+// and s_wave free for the scan that follows; a kernel that is one scan
+// just ends.
 #define VL_SCAN_THREADS 1024u
+template <bool MAX, bool PARK, typename T, typename F>
+__device__ __forceinline__ void block_scan(F value, uint64_t count, T* out,
+                                           T* s_wave) {
+  auto op = [](T a, T b) { return MAX ? (a > b ? a : b) : (T)(a + b); };
+  const uint32_t lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const uint64_t per = (count + VL_SCAN_THREADS - 1) / VL_SCAN_THREADS * WAVE;
+  const uint64_t b = min(wv * per, count);
+  const uint64_t e = min(b + per, count);
+  T sum = 0;
+  for (uint64_t i = b + lane; i < e; i += WAVE) {
+    const T k = value(i);
+    if (PARK) out[i] = k;
+    sum = op(sum, k);
+  }
+  for (uint32_t o = WAVE / 2; o; o >>= 1)
+    sum = op(sum, __shfl_xor(sum, o, WAVE));
+  if (lane == 0) s_wave[wv] = sum;
+  __syncthreads();
+  T at = 0;  // what the items before the tile at hand amount to
+  for (uint32_t w = 0; w < wv; w++) at = op(at, s_wave[w]);
+  for (uint64_t i0 = b; i0 < e; i0 += WAVE) {  // uniform trip count
+    const uint64_t i = i0 + lane;
+    const T k = i < e ? (PARK ? out[i] : value(i)) : 0;
+    T inc = k;  // inclusive scan over the tile
+    for (uint32_t o = 1; o < WAVE; o <<= 1) {
+      T v = __shfl_up(inc, o, WAVE);
+      if (lane >= o) inc = op(inc, v);
+    }
+    if (i < e) out[i] = MAX ? op(at, inc) : (T)(at + inc - k);
+    at = op(at, __shfl(inc, WAVE - 1, WAVE));
+  }
+  // the last wave's segment ends at count: its carry is the total
+  if (!MAX && threadIdx.x == VL_SCAN_THREADS - 1) out[count] = at;
+  if (PARK) __syncthreads();
+}
+
 __global__ void __launch_bounds__(VL_SCAN_THREADS) k_vl_scan(
     const uint64_t* __restrict__ lens, uint32_t n,
     uint64_t* __restrict__ cstart) {
   __shared__ uint64_t s_wave[VL_SCAN_THREADS / WAVE];
-  const uint32_t lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const uint64_t per =
-      ((uint64_t)n + VL_SCAN_THREADS - 1) / VL_SCAN_THREADS * WAVE;
-  const uint64_t b = min(wv * per, (uint64_t)n);
-  const uint64_t e = min(b + per, (uint64_t)n);
-  uint64_t sum = 0;
-  for (uint64_t i = b + lane; i < e; i += WAVE)
-    sum += rocp2p_vl_chunks(lens[i]);
-  for (uint32_t o = WAVE / 2; o; o >>= 1) sum += __shfl_xor(sum, o, WAVE);
-  if (lane == 0) s_wave[wv] = sum;
-  __syncthreads();
-  uint64_t at = 0;  // chunks before the tile at hand
-  for (uint32_t w = 0; w < wv; w++) at += s_wave[w];
-  for (uint64_t i0 = b; i0 < e; i0 += WAVE) {  // uniform trip count
-    const uint64_t i = i0 + lane;
-    const uint64_t k = i < e ? rocp2p_vl_chunks(lens[i]) : 0;
-    uint64_t inc = k;  // inclusive scan over the tile
-    for (uint32_t o = 1; o < WAVE; o <<= 1) {
-      uint64_t v = __shfl_up(inc, o, WAVE);
-      if (lane >= o) inc += v;
-    }
-    if (i < e) cstart[i] = at + inc - k;
-    at += __shfl(inc, WAVE - 1, WAVE);
-  }
-  // the last wave's segment ends at n: its carry is the total
-  if (threadIdx.x == VL_SCAN_THREADS - 1) cstart[n] = at;
+  block_scan<false, false>(
+      [&](uint64_t i) { return rocp2p_vl_chunks(lens[i]); }, n, cstart,
+      s_wave);
 }
 
-// zlib crc32 of a full 4 KiB chunk held the engine's way (lane l: pieces
-// l, l+64, l+128, l+192), in every lane: k_msg_engine_crc's algebra.
-__device__ __forceinline__ uint32_t icrc_chunk_full(const icrc_lds& s,
-                                                    const uint4& v0,
-                                                    const uint4& v1,
-                                                    const uint4& v2,
-                                                    const uint4& v3,
-                                                    uint32_t lane) {
-  uint32_t crc = crc_piece16(s.t.slice, v0);
-  crc = rocp2p_crc_apply(s.t.shift[4], crc) ^ crc_piece16(s.t.slice, v1);
-  crc = rocp2p_crc_apply(s.t.shift[4], crc) ^ crc_piece16(s.t.slice, v2);
-  crc = rocp2p_crc_apply(s.t.shift[4], crc) ^ crc_piece16(s.t.slice, v3);
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    uint32_t partner = __shfl_xor(crc, 1u << k, WAVE);
-    bool is_left = ((lane >> k) & 1u) == 0;
-    uint32_t cl = is_left ? crc : partner;
-    uint32_t cr = is_left ? partner : crc;
-    crc = rocp2p_crc_apply(k < 2 ? s.shift16[k] : s.t.shift[k - 2], cl) ^ cr;
-  }
-  return crc;
-}
-
-// Merge the pending shares (runs that ended inside a message) of a
-// workgroup's waves: adjacent waves own adjacent runs, so equal targets
-// are adjacent.  s_pend: 2 * nwv words of LDS that are dead by now; the
-// caller has passed the barrier that says so.
-__device__ __forceinline__ void vl_merge_pending(uint32_t* s_pend,
-                                                 uint32_t lane, uint32_t wv,
-                                                 uint32_t nwv, uint32_t pend_f,
-                                                 uint32_t pend_m,
-                                                 uint32_t* __restrict__ out) {
-  if (lane == 0) {
-    s_pend[2 * wv] = pend_f;
-    s_pend[2 * wv + 1] = pend_m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t f = s_pend[0], fm = s_pend[1];
-    for (uint32_t w = 1; w < nwv; w++) {
-      if (s_pend[2 * w + 1] != fm) {
-        if (f) atomicXor(&out[fm], f);
-        f = 0;
-        fm = s_pend[2 * w + 1];
-      }
-      f ^= s_pend[2 * w];
-    }
-    if (f) atomicXor(&out[fm], f);
-  }
-}
-
-// The plain form keeps nothing in LDS.
-template <bool ICRC>
-struct vl_engine_lds {};
-template <>
-struct vl_engine_lds<true> {
-  icrc_lds t;
-};
-
-// The message engine for per-message lengths (multiples of 16), with
-// (ICRC) or without the inline digest: one kernel, so both forms move
-// bytes the same way — 1 KiB-contiguous wave accesses, lane l holding
-// pieces l, l+64, l+128, l+192 of a chunk.  Without ICRC no table is
-// staged and no CRC work is done.  The wave index is made provably
-// uniform, so the cursor and the descriptors it loads live in SGPRs.
+// The message engine for per-message lengths (multiples of 16).
 template <bool GATHER, bool ICRC>
 __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_v(
     uint8_t* __restrict__ region, const uint64_t* __restrict__ offs,
@@ -807,103 +998,11 @@ __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_v(
     const uint64_t* __restrict__ cstart, uint32_t n,
     uint32_t* __restrict__ out) {
   __shared__ vl_engine_lds<ICRC> s;
-  if constexpr (ICRC) {
-    for (uint32_t i = threadIdx.x; i < 2 * 4 * 256; i += blockDim.x)
-      (&s.t.shift16[0][0][0])[i] = (&c_crc.shift16[0][0][0])[i];
-    crc_stage_tables(s.t.t);
-  }
-
-  const uint32_t lane = threadIdx.x & (WAVE - 1);
-  const uint32_t wv =
-      (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
-  const uint32_t nwv = blockDim.x / WAVE;
-  uint64_t c0, c1;
-  rocp2p_vl_run(cstart[n], (uint64_t)gridDim.x * nwv,
-                (uint64_t)blockIdx.x * nwv + wv, &c0, &c1);
-
-  rocp2p_vl_cursor cur = {0, 0, 0, 0};
-  // this message on the side that is read and on the side that is written
-  const uint8_t* from = nullptr;
-  uint8_t* to = nullptr;
-  auto open_msg = [&](uint64_t msg) {
-    uint8_t* inside = region + offs[msg];
-    uint8_t* outside = reinterpret_cast<uint8_t*>(addrs[msg]);
-    from = GATHER ? outside : inside;
-    to = GATHER ? inside : outside;
-  };
-  if (c0 < c1) {
-    rocp2p_vl_seek(&cur, cstart, lens, n, c0);
-    open_msg(cur.m);
-  }
-  uint32_t acc = 0;  // crc of this run's full chunks of message m so far
-  uint32_t pend_f = 0, pend_m = 0;
-
-  for (uint64_t c = c0; c < c1; c++) {
-    const uint64_t pos = cur.ci * PAGE;
-    const uint64_t left = cur.len - pos;  // > 0, a multiple of 16
-    const uint4* src = reinterpret_cast<const uint4*>(from + pos);
-    uint4* dst = reinterpret_cast<uint4*>(to + pos);
-    uint64_t done;  // message bytes [.., done) are covered by acc
-    if (left >= PAGE) {
-      // four named registers, not an array: the plain form would
-      // otherwise get the array promoted to LDS
-      const uint4 v0 = src[lane], v1 = src[lane + WAVE];
-      const uint4 v2 = src[lane + 2 * WAVE], v3 = src[lane + 3 * WAVE];
-      dst[lane] = v0;
-      dst[lane + WAVE] = v1;
-      dst[lane + 2 * WAVE] = v2;
-      dst[lane + 3 * WAVE] = v3;
-      if constexpr (ICRC)
-        acc = rocp2p_crc_apply(s.t.t.shift[5],
-                               rocp2p_crc_apply(s.t.t.shift[5], acc)) ^
-              icrc_chunk_full(s.t, v0, v1, v2, v3, lane);
-      done = pos + PAGE;
-    } else {
-      const uint32_t valid = (uint32_t)left;  // 16..4080
-      const uint32_t nvec = valid / 16;
-      uint32_t x = 0;
-#pragma unroll
-      for (uint32_t u = 0; u < 4; u++) {
-        const uint32_t q = lane + WAVE * u;
-        if (q < nvec) {
-          uint4 v = src[q];
-          dst[q] = v;
-          if constexpr (ICRC)
-            x ^= rocp2p_crc_mulmod(
-                rocp2p_crc_xpow8(valid - 16 * (q + 1), c_crc.xpow8),
-                crc_piece16(s.t.t.slice, v));
-        }
-      }
-      if constexpr (ICRC) {
-        for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
-        if (lane == 0) atomicXor(&out[cur.m], x);
-      }
-      done = pos;  // acc (if any) still has `valid` bytes after it
-    }
-    if constexpr (ICRC) {
-      const bool msg_end = cur.ci + 1 == cur.cpm;
-      if (msg_end || c + 1 == c1) {
-        if (acc) {  // a zero CRC contributes nothing wherever it sits
-          const uint64_t r = cur.len - done;
-          uint32_t f = acc;
-          if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
-          if (msg_end) {
-            if (lane == 0) atomicXor(&out[cur.m], f);
-          } else {
-            pend_f = f;
-            pend_m = (uint32_t)cur.m;
-          }
-        }
-        acc = 0;
-      }
-    }
-    if (c + 1 < c1 && rocp2p_vl_next(&cur, cstart, lens)) open_msg(cur.m);
-  }
-
-  if constexpr (ICRC) {
-    __syncthreads();  // the tables are dead: their first words hand off
-    vl_merge_pending(&s.t.t.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
-  }
+  if constexpr (ICRC) icrc_stage_tables(s.t);
+  wave_run w = wave_run_open(blockDim.x / WAVE);
+  w.split(cstart[n]);
+  msg_engine_walk<GATHER, ICRC>(s, w, vl_batch{cstart, lens, n}, region, offs,
+                                addrs, out);
 }
 
 // k_crc32_msgs for per-message lengths (any byte count, 0 included):
@@ -976,7 +1075,7 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs_v(
   }
 
   __syncthreads();  // the tables are dead: their first words hand off
-  vl_merge_pending(&s.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
+  crc_merge_pending(&s.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
 }
 
 // ---------------------------------------------------------------------
@@ -987,7 +1086,7 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs_v(
 // count therefore depends on the store-side skew (dst & 15) as well as
 // on the length — k_vl_scan_b reads both.  Runs, the one binary search,
 // the forward cursor, the running CRC, the end-of-run shift and the
-// pending-share merge are k_msg_engine_v's, unchanged.
+// pending-share merge are the run walk's, unchanged.
 //
 // The side that is read is loaded as aligned 16-byte granules too and
 // realigned in registers by rel = (src - dst) & 15, which is uniform
@@ -1016,6 +1115,23 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs_v(
 // shifted by the message bytes behind them, straight into the digest.
 // acc covers full chunks only and is flushed before anything else of
 // the message is accounted for.
+//
+// Scatter/gather lists (geometry: p2p_sgl.h) run on the same walk with
+// the SGE as the work item.  A message is the concatenation of its
+// SGEs: a gather reads them from anywhere outside and writes them back
+// to back into the region, a scatter cuts the contiguous region range
+// over them.  A scan kernel (k_sg_scan) turns the lists into what the
+// walk takes per item — the address written, the address read, the
+// length, the chunk prefix sums — plus the two things only the digest
+// needs: the message that owns the SGE and the message bytes behind it
+// (its tail).  Consecutive SGEs of a message meet inside a granule of
+// the region like neighbouring messages do, which the narrow stores of
+// p2p_bytes.h already allow.  A CRC piece of SGE j is shifted by the
+// bytes behind it in the SGE and by tail[j] more, and is XORed into
+// out[owner[j]]; the pending merge keys on the owner as well (owners
+// are nondecreasing in the SGE index, so equal targets stay adjacent).
+// A message without SGEs, and an SGE without bytes, own no chunk and
+// reach no load, store or atomic.
 
 // k_vl_scan for the byte-granular grid: where[m] is the address (or the
 // offset from a 16-byte-aligned base) message m is written at.
@@ -1023,33 +1139,11 @@ __global__ void __launch_bounds__(VL_SCAN_THREADS) k_vl_scan_b(
     const uint64_t* __restrict__ lens, const uint64_t* __restrict__ where,
     uint32_t n, uint64_t* __restrict__ cstart) {
   __shared__ uint64_t s_wave[VL_SCAN_THREADS / WAVE];
-  const uint32_t lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const uint64_t per =
-      ((uint64_t)n + VL_SCAN_THREADS - 1) / VL_SCAN_THREADS * WAVE;
-  const uint64_t b = min(wv * per, (uint64_t)n);
-  const uint64_t e = min(b + per, (uint64_t)n);
-  uint64_t sum = 0;
-  for (uint64_t i = b + lane; i < e; i += WAVE)
-    sum += rocp2p_b_chunks((uint32_t)where[i] & 15u, lens[i]);
-  for (uint32_t o = WAVE / 2; o; o >>= 1) sum += __shfl_xor(sum, o, WAVE);
-  if (lane == 0) s_wave[wv] = sum;
-  __syncthreads();
-  uint64_t at = 0;  // chunks before the tile at hand
-  for (uint32_t w = 0; w < wv; w++) at += s_wave[w];
-  for (uint64_t i0 = b; i0 < e; i0 += WAVE) {  // uniform trip count
-    const uint64_t i = i0 + lane;
-    const uint64_t k =
-        i < e ? rocp2p_b_chunks((uint32_t)where[i] & 15u, lens[i]) : 0;
-    uint64_t inc = k;  // inclusive scan over the tile
-    for (uint32_t o = 1; o < WAVE; o <<= 1) {
-      uint64_t v = __shfl_up(inc, o, WAVE);
-      if (lane >= o) inc += v;
-    }
-    if (i < e) cstart[i] = at + inc - k;
-    at += __shfl(inc, WAVE - 1, WAVE);
-  }
-  // the last wave's segment ends at n: its carry is the total
-  if (threadIdx.x == VL_SCAN_THREADS - 1) cstart[n] = at;
+  block_scan<false, false>(
+      [&](uint64_t i) {
+        return rocp2p_b_chunks((uint32_t)where[i] & 15u, lens[i]);
+      },
+      n, cstart, s_wave);
 }
 
 // The granule the next lane holds; lane 63 gets lane 0's.
@@ -1122,6 +1216,8 @@ __device__ __forceinline__ uint4 g16_u4(const rocp2p_g16& v) {
 // without the inline digest.  Same launch shape, descriptors and scratch
 // as k_msg_engine_v; cstart comes from k_vl_scan_b over the side that is
 // written.  Without ICRC no table is staged and no CRC work is done.
+// Its own body, not a walk shared with k_msg_engine_sg: on a shared body
+// the plain gathers of both measured 1.1-1.6% slower (docs/PERF.md §8).
 template <bool GATHER, bool ICRC>
 __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_b(
     uint8_t* __restrict__ region, const uint64_t* __restrict__ offs,
@@ -1175,7 +1271,7 @@ __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_b(
     const uint8_t* sp = from0 + p0;
     uint8_t* dp = to0 + p0;
     const bool full = rocp2p_b_full(skew, rel, cur.len, cur.ci);
-    // four named registers, not an array: see k_msg_engine_v
+    // four named registers, not an array: see msg_engine_walk
     rocp2p_g16 v0, v1, v2, v3;
     uint64_t done;  // store-stream bytes [.., done) are covered by acc
     if (full) {
@@ -1271,7 +1367,7 @@ __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_b(
 
   if constexpr (ICRC) {
     __syncthreads();  // the tables are dead: their first words hand off
-    vl_merge_pending(&s.t.t.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
+    crc_merge_pending(&s.t.t.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
   }
 }
 
@@ -1287,171 +1383,88 @@ __global__ void __launch_bounds__(WAVE * CRC_DIGEST_WAVES) k_crc32_msgs_b(
     uint32_t n, uint32_t* __restrict__ out) {
   __shared__ crc_lds s;
   crc_stage_tables(s);
+  wave_run w = wave_run_open(blockDim.x / WAVE);
+  w.split(cstart[n]);
+  const uint32_t lane = w.lane;
+  const vl_batch batch = {cstart, lens, n};
 
-  const uint32_t lane = threadIdx.x & (WAVE - 1);
-  const uint32_t wv =
-      (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
-  const uint32_t nwv = blockDim.x / WAVE;
-  uint64_t c0, c1;
-  rocp2p_vl_run(cstart[n], (uint64_t)gridDim.x * nwv,
-                (uint64_t)blockIdx.x * nwv + wv, &c0, &c1);
-
-  rocp2p_vl_cursor cur = {0, 0, 0, 0};
-  const uint8_t* mp0 = base;  // where the message's stream starts
-  uint32_t skew = 0;
-  auto open_msg = [&](uint64_t msg) {
-    const uint64_t off = offs[msg];
-    skew = (uint32_t)off & 15u;
-    mp0 = base + (off - skew);
-  };
-  if (c0 < c1) {
-    rocp2p_vl_seek(&cur, cstart, lens, n, c0);
+  crc_run crc;
+  if (w.c0 < w.c1) {
+    rocp2p_vl_cursor cur;
+    const uint8_t* mp0 = base;  // where the message's stream starts
+    uint32_t skew = 0;
+    auto open_msg = [&](uint64_t msg) {
+      const uint64_t off = offs[msg];
+      skew = (uint32_t)off & 15u;
+      mp0 = base + (off - skew);
+    };
+    batch.seek(&cur, w.c0);
     open_msg(cur.m);
-  }
-  uint32_t acc = 0;  // crc of this run's full chunks of message m so far
-  uint32_t pend_f = 0, pend_m = 0;
 
-  for (uint64_t c = c0; c < c1; c++) {
-    const uint64_t p0 = cur.ci * PAGE;    // of the message's stream
-    const uint64_t end = skew + cur.len;  // of the message, likewise
-    const uint8_t* seg = mp0 + p0 + lane * SEG;
-    const bool full = rocp2p_b_full(skew, 0, cur.len, cur.ci);
-    uint64_t done;  // stream bytes [.., done) are covered by acc
-    if (full) {
-      acc = rocp2p_crc_apply(s.shift[5], rocp2p_crc_apply(s.shift[5], acc)) ^
-            crc_page(seg, lane, s);
-      done = p0 + PAGE;
-    } else {
-      // the chunk's valid bytes, and this lane's [a, b) of its 64
-      const uint32_t lo = p0 < skew ? skew : 0u;  // first chunk only
-      const uint32_t hi = (uint32_t)min(end - p0, (uint64_t)PAGE);
-      const uint32_t beg = lane * SEG;
-      const uint32_t a = lo > beg ? min(lo - beg, SEG) : 0u;  // < 16
-      const uint32_t b = hi > beg ? min(hi - beg, SEG) : 0u;
-      uint32_t x = 0;
-      if (a < b) {
-        const uint64_t g0 = cur.ci * ROCP2P_B_PER_CHUNK + lane * 4;
-        uint64_t d[9];
+    for (uint64_t c = w.c0; c < w.c1; c++) {
+      const uint64_t p0 = cur.ci * PAGE;    // of the message's stream
+      const uint64_t end = skew + cur.len;  // of the message, likewise
+      const uint8_t* seg = mp0 + p0 + lane * SEG;
+      const bool full = rocp2p_b_full(skew, 0, cur.len, cur.ci);
+      uint64_t done;  // stream bytes [.., done) are covered by acc
+      if (full) {
+        crc.full_chunk(s, crc_page(seg, lane, s));
+        done = p0 + PAGE;
+      } else {
+        // the chunk's valid bytes, and this lane's [a, b) of its 64
+        const uint32_t lo = p0 < skew ? skew : 0u;  // first chunk only
+        const uint32_t hi = (uint32_t)min(end - p0, (uint64_t)PAGE);
+        const uint32_t beg = lane * SEG;
+        const uint32_t a = lo > beg ? min(lo - beg, SEG) : 0u;  // < 16
+        const uint32_t b = hi > beg ? min(hi - beg, SEG) : 0u;
+        uint32_t x = 0;
+        if (a < b) {
+          const uint64_t g0 = cur.ci * ROCP2P_B_PER_CHUNK + lane * 4;
+          uint64_t d[9];
 #pragma unroll
-        for (uint32_t q = 0; q < 4; q++) {
-          uint32_t glo, ghi;
-          rocp2p_b_range(skew, end, g0 + q, &glo, &ghi);
-          const rocp2p_g16 v =
-              rocp2p_b_load(seg + ROCP2P_B_GRAN * q, glo, ghi);
-          d[2 * q] = v.x | ((uint64_t)v.y << 32);
-          d[2 * q + 1] = v.z | ((uint64_t)v.w << 32);
-        }
-        d[8] = 0;
-        if (a) {  // bring byte a down to byte 0
-          if (a >= 8) {
-#pragma unroll
-            for (uint32_t i = 0; i < 8; i++) d[i] = d[i + 1];
+          for (uint32_t q = 0; q < 4; q++) {
+            uint32_t glo, ghi;
+            rocp2p_b_range(skew, end, g0 + q, &glo, &ghi);
+            const rocp2p_g16 v =
+                rocp2p_b_load(seg + ROCP2P_B_GRAN * q, glo, ghi);
+            d[2 * q] = v.x | ((uint64_t)v.y << 32);
+            d[2 * q + 1] = v.z | ((uint64_t)v.w << 32);
           }
-          const uint32_t sh = 8 * (a & 7);
-          if (sh) {
+          d[8] = 0;
+          if (a) {  // bring byte a down to byte 0
+            if (a >= 8) {
 #pragma unroll
-            for (uint32_t i = 0; i < 8; i++)
-              d[i] = (d[i] >> sh) | (d[i + 1] << (64 - sh));
+              for (uint32_t i = 0; i < 8; i++) d[i] = d[i + 1];
+            }
+            const uint32_t sh = 8 * (a & 7);
+            if (sh) {
+#pragma unroll
+              for (uint32_t i = 0; i < 8; i++)
+                d[i] = (d[i] >> sh) | (d[i + 1] << (64 - sh));
+            }
           }
-        }
-        uint32_t w[16];
+          uint32_t wd[16];
 #pragma unroll
-        for (uint32_t i = 0; i < 8; i++) {
-          w[2 * i] = (uint32_t)d[i];
-          w[2 * i + 1] = (uint32_t)(d[i] >> 32);
+          for (uint32_t i = 0; i < 8; i++) {
+            wd[2 * i] = (uint32_t)d[i];
+            wd[2 * i + 1] = (uint32_t)(d[i] >> 32);
+          }
+          x = rocp2p_crc_mulmod(
+              rocp2p_crc_xpow8(end - (p0 + beg + b), c_crc.xpow8),
+              crc_bytes64(s.slice, wd, b - a));
         }
-        x = rocp2p_crc_mulmod(
-            rocp2p_crc_xpow8(end - (p0 + beg + b), c_crc.xpow8),
-            crc_bytes64(s.slice, w, b - a));
+        crc_wave_emit(x, 0, lane, &out[cur.m]);
+        done = p0;  // acc (if any) ends where this chunk begins
       }
-      for (unsigned o = WAVE / 2; o; o >>= 1) x ^= __shfl_xor(x, o, WAVE);
-      if (lane == 0) atomicXor(&out[cur.m], x);
-      done = p0;  // acc (if any) ends where this chunk begins
+      crc.flush(cur.ci + 1 == cur.cpm, c + 1 == w.c1, full, end - done,
+                (uint32_t)cur.m, lane, out);
+      if (c + 1 < w.c1 && batch.next(&cur)) open_msg(cur.m);
     }
-    const bool msg_end = cur.ci + 1 == cur.cpm;
-    const bool run_end = c + 1 == c1;
-    if (msg_end || run_end || !full) {
-      if (acc) {  // a zero CRC contributes nothing wherever it sits
-        const uint64_t r = end - done;
-        uint32_t f = acc;
-        if (r) f = rocp2p_crc_mulmod(crc_xpow_wave(r, lane), acc);
-        if (run_end && !msg_end) {
-          pend_f = f;
-          pend_m = (uint32_t)cur.m;
-        } else if (lane == 0) {
-          atomicXor(&out[cur.m], f);
-        }
-      }
-      acc = 0;
-    }
-    if (c + 1 < c1 && rocp2p_vl_next(&cur, cstart, lens)) open_msg(cur.m);
   }
-
-  __syncthreads();  // the tables are dead: their first words hand off
-  vl_merge_pending(&s.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
+  crc.merge(&s.slice[0][0], w, out);
 }
 
 // ---------------------------------------------------------------------
-// Scatter/gather lists (geometry: p2p_sgl.h).  A message is the
-// concatenation of its SGEs: a gather reads them from anywhere outside
-// and writes them back to back into the region, a scatter cuts the
-// contiguous region range over them.  The work item is the SGE.  A scan
-// kernel (k_sg_scan) turns the lists into what k_msg_engine_b takes per message —
-// the address written, the address read, the length, the chunk prefix
-// sums — plus the two things only the digest needs: the message that
-// owns the SGE and the message bytes behind it.  The engine then is
-// k_msg_engine_b over SGEs; consecutive SGEs of a message meet inside a
-// granule of the region like neighbouring messages do, which the narrow
-// stores of p2p_bytes.h already allow.
-//
-// ICRC: a CRC piece of SGE j is shifted by the bytes behind it in the
-// SGE, as before, and by tail[j] more, and is XORed into out[owner[j]]:
-// crc(A || B) = shift(crc(A), |B|) ^ crc(B) does not care where a
-// message is cut.  A message without SGEs, and an SGE without bytes, own
-// no chunk and reach no load, store or atomic.
-
-// A scan of value(0 .. count - 1) by one workgroup of VL_SCAN_THREADS:
-// k_vl_scan's two passes, with the values parked in out between them so
-// that value() runs once per item (the same lane owns an item in both
-// passes).  Sums (MAX false) are exclusive, out[0 .. count] with the
-// total last; running maxima (MAX true) are inclusive, out[0 .. count).
-// Ends with a barrier: out is complete and s_wave free again.
-template <bool MAX, typename T, typename F>
-__device__ __forceinline__ void sg_block_scan(F value, uint64_t count, T* out,
-                                              T* s_wave) {
-  auto op = [](T a, T b) { return MAX ? (a > b ? a : b) : (T)(a + b); };
-  const uint32_t lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const uint64_t per = (count + VL_SCAN_THREADS - 1) / VL_SCAN_THREADS * WAVE;
-  const uint64_t b = min(wv * per, count);
-  const uint64_t e = min(b + per, count);
-  T sum = 0;
-  for (uint64_t i = b + lane; i < e; i += WAVE) {
-    const T k = value(i);
-    out[i] = k;
-    sum = op(sum, k);
-  }
-  for (uint32_t o = WAVE / 2; o; o >>= 1)
-    sum = op(sum, __shfl_xor(sum, o, WAVE));
-  if (lane == 0) s_wave[wv] = sum;
-  __syncthreads();
-  T at = 0;  // what the items before the tile at hand amount to
-  for (uint32_t w = 0; w < wv; w++) at = op(at, s_wave[w]);
-  for (uint64_t i0 = b; i0 < e; i0 += WAVE) {  // uniform trip count
-    const uint64_t i = i0 + lane;
-    const T k = i < e ? out[i] : 0;
-    T inc = k;  // inclusive scan over the tile
-    for (uint32_t o = 1; o < WAVE; o <<= 1) {
-      T v = __shfl_up(inc, o, WAVE);
-      if (lane >= o) inc = op(inc, v);
-    }
-    if (i < e) out[i] = MAX ? op(at, inc) : (T)(at + inc - k);
-    at = op(at, __shfl(inc, WAVE - 1, WAVE));
-  }
-  // the last wave's segment ends at count: its carry is the total
-  if (!MAX && threadIdx.x == VL_SCAN_THREADS - 1) out[count] = at;
-  __syncthreads();
-}
-
 // The scan pass of a scatter/gather batch: one workgroup, one launch.
 // Owners first: every message with SGEs writes its number at its first
 // SGE and a running maximum spreads it over the others (message numbers
@@ -1474,12 +1487,12 @@ __global__ void __launch_bounds__(VL_SCAN_THREADS) k_sg_scan(
   for (uint32_t m = threadIdx.x; m < n; m += VL_SCAN_THREADS)
     if (rocp2p_sgl_has_sges(sge_start, m)) v.owner[sge_start[m]] = m;
   __syncthreads();
-  sg_block_scan<true>([&](uint64_t j) { return v.owner[j]; }, nsge, v.owner,
-                      s_own);
-  sg_block_scan<false>([&](uint64_t j) { return sge_lens[j]; }, nsge,
-                       v.prefix, s_wave);
+  block_scan<true, true>([&](uint64_t j) { return v.owner[j]; }, nsge,
+                         v.owner, s_own);
+  block_scan<false, true>([&](uint64_t j) { return sge_lens[j]; }, nsge,
+                          v.prefix, s_wave);
   const uint64_t base = reinterpret_cast<uintptr_t>(region);
-  sg_block_scan<false>(
+  block_scan<false, true>(
       [&](uint64_t j) {
         return rocp2p_sgl_item(v, base, offs, sge_start, sge_addrs, j,
                                GATHER);
@@ -1489,13 +1502,12 @@ __global__ void __launch_bounds__(VL_SCAN_THREADS) k_sg_scan(
 
 // k_msg_engine_b with the SGE as its work item: the same launch shape,
 // run split, cursor and chunk bodies, over the nsge SGEs that k_sg_scan
-// laid out in scratch (rocp2p_sgl_view).  The scan has resolved the direction (to / from
-// are addresses), so a gather and a scatter are the same code here.
-// Every CRC contribution carries the SGE's tail as a further shift and
-// goes to the digest of the owning message; the pending merge keys on
-// the owner as well (owners are nondecreasing in the SGE index, so equal
-// targets stay adjacent).  Without ICRC no table is staged and no CRC
-// work is done.
+// laid out in scratch (rocp2p_sgl_view).  The scan has resolved the
+// direction (to / from are addresses), so a gather and a scatter are the
+// same code here.  Every CRC contribution carries the SGE's tail as a
+// further shift and goes to the digest of the owning message; the
+// pending merge keys on the owner as well.  Without ICRC no table is
+// staged and no CRC work is done.
 template <bool ICRC>
 __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_sg(
     const uint64_t* __restrict__ sge_lens, const uint64_t* __restrict__ cstart,
@@ -1550,7 +1562,7 @@ __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_sg(
     const uint8_t* sp = from0 + p0;
     uint8_t* dp = to0 + p0;
     const bool full = rocp2p_b_full(skew, rel, cur.len, cur.ci);
-    // four named registers, not an array: see k_msg_engine_v
+    // four named registers, not an array: see msg_engine_walk
     rocp2p_g16 v0, v1, v2, v3;
     uint64_t done;  // store-stream bytes [.., done) are covered by acc
     if (full) {
@@ -1649,7 +1661,7 @@ __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_sg(
 
   if constexpr (ICRC) {
     __syncthreads();  // the tables are dead: their first words hand off
-    vl_merge_pending(&s.t.t.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
+    crc_merge_pending(&s.t.t.slice[0][0], lane, wv, nwv, pend_f, pend_m, out);
   }
 }
 
@@ -1780,14 +1792,51 @@ static hipError_t crc_tables_ready() {
   return e;
 }
 
-// Inline-ICRC engine launch: 4-wave workgroups, one chunk per wave until
-// the grid is full, longer runs after that.  The grid stays under the
-// plain engine's cap and, measured on MI355X, under 128 workgroups: the
-// fused gather loses to its own outstanding PCIe reads beyond that
-// (1 MiB-class messages: 49.9 GB/s at 512 workgroups, 52.9 at 256, 54.0
-// at 128, 53.6 at 64; the scatter direction does not care).
-// grid_cap != 0 caps the workgroup count further.
+// What every launch that digests does first: the tables, and n zeroed
+// digests for the kernels to XOR into.
+static hipError_t crc_out_ready(uint32_t* d_out, uint32_t n,
+                                hipStream_t stream) {
+  hipError_t e = crc_tables_ready();
+  if (e != hipSuccess) return e;
+  return hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+}
+
+// Workgroup cap of the chunk-walking engines (4-wave workgroups, one
+// chunk per wave until the grid is full, longer runs after that).
+// The fused forms stay under the plain engine's cap and, measured on
+// MI355X, under 128 workgroups: the fused gather loses to its own
+// outstanding PCIe reads beyond that (1 MiB-class messages: 49.9 GB/s at
+// 512 workgroups, 52.9 at 256, 54.0 at 128, 53.6 at 64; the scatter
+// direction does not care).  The plain gather has the same four 16-byte
+// PCIe reads per lane in flight and, measured on MI355X, the same
+// optimum (4 KiB and 1 MiB messages: 53.0 GB/s at 512 workgroups, 53.5
+// at 256, 56.1-56.7 at 128 and 64); only batches known to hold sub-chunk
+// messages (0 < max_msg_bytes < 4096), whose waves have few lanes busy,
+// do better with the full cap (64 B: 19.6 GB/s at 128, 22.4 at 512).
+// The plain scatter does not care from 4 KiB up and wants the full cap
+// at 64 B (21.5 at 128, 26.1 at 512).  The byte-granular and the
+// scatter/gather engines take the same caps until measurements say
+// otherwise (docs/PERF.md).  grid_cap != 0 caps the count further.
 #define ICRC_GRID 128u
+static uint64_t engine_grid_cap(bool gather, bool icrc, uint64_t max_msg_bytes,
+                                uint32_t grid_cap) {
+  uint64_t cap = gather_grid_cap();
+  const bool small = max_msg_bytes && max_msg_bytes < PAGE;
+  if ((icrc || (gather && !small)) && cap > ICRC_GRID) cap = ICRC_GRID;
+  if (grid_cap && grid_cap < cap) cap = grid_cap;
+  return cap;
+}
+
+// Launch an engine's fused form when there are digests to write, its
+// plain form otherwise; both take the same arguments.
+template <typename K, typename... A>
+static hipError_t engine_launch(K fused, K plain, uint32_t* d_out,
+                                uint32_t grid, hipStream_t stream, A... args) {
+  hipLaunchKernelGGL(d_out ? fused : plain, dim3(grid),
+                     dim3(WAVE * ICRC_WAVES), 0, stream, args..., d_out);
+  return hipGetLastError();
+}
+
 template <bool GATHER>
 static hipError_t msg_engine_crc_launch(void* region, const uint64_t* d_offs,
                                         const uint64_t* d_addrs,
@@ -1796,18 +1845,14 @@ static hipError_t msg_engine_crc_launch(void* region, const uint64_t* d_offs,
                                         hipStream_t stream) {
   if (msg_bytes % 16 || !msg_bytes) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
-  hipError_t e = crc_tables_ready();
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+  hipError_t e = crc_out_ready(d_out, n, stream);
   if (e != hipSuccess) return e;
   uint64_t cpm = msg_bytes / PAGE + (msg_bytes % PAGE != 0);
   uint64_t total;
   if (__builtin_mul_overflow(cpm, (uint64_t)n, &total))
     return hipErrorInvalidValue;
   const uint64_t W = ICRC_WAVES;
-  uint64_t cap = gather_grid_cap();
-  if (cap > ICRC_GRID) cap = ICRC_GRID;
-  if (grid_cap && grid_cap < cap) cap = grid_cap;
+  const uint64_t cap = engine_grid_cap(GATHER, true, 0, grid_cap);
   uint64_t blocks = (total + W - 1) / W;
   if (blocks > cap) blocks = cap;
   uint64_t run = (total + W * blocks - 1) / (W * blocks);
@@ -1859,14 +1904,16 @@ extern "C" hipError_t rocp2p_crc32_pages(const void* buf, uint64_t npages,
 // workgroups beat 4- and 8-wave ones by 2-15% from 64 MiB up: one table
 // copy per CU and 16 pending shares merged into one atomic.
 // grid_cap != 0 caps the workgroup count instead of 256.
+static uint64_t digest_grid_cap(uint32_t grid_cap) {
+  return grid_cap ? grid_cap : 256;
+}
+
 static hipError_t crc32_digest_launch(const void* base,
                                       const uint64_t* d_offs,
                                       uint64_t msg_bytes, uint32_t n,
                                       uint32_t* d_out, uint32_t grid_cap,
                                       hipStream_t stream) {
-  hipError_t e = crc_tables_ready();
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+  hipError_t e = crc_out_ready(d_out, n, stream);
   if (e != hipSuccess) return e;
   if (!msg_bytes) return hipSuccess;  // crc32 of nothing is 0
   uint64_t cpm = msg_bytes / PAGE + (msg_bytes % PAGE != 0);
@@ -1874,7 +1921,7 @@ static hipError_t crc32_digest_launch(const void* base,
   if (__builtin_mul_overflow(cpm, (uint64_t)n, &total))
     return hipErrorInvalidValue;
   const uint64_t W = CRC_DIGEST_WAVES;
-  uint64_t cap = grid_cap ? grid_cap : 256;
+  const uint64_t cap = digest_grid_cap(grid_cap);
   uint64_t blocks = (total + W - 1) / W;
   if (blocks > cap) blocks = cap;
   uint64_t run = (total + W * blocks - 1) / (W * blocks);
@@ -1912,13 +1959,16 @@ extern "C" hipError_t rocp2p_crc32_region(const void* buf, uint64_t nbytes,
 // unknown, take the cap): it sizes the grid and nothing else, the
 // kernels take the real total from d_cstart[n].
 
-static uint32_t vl_grid(uint32_t n, uint64_t max_msg_bytes, uint64_t waves,
-                        uint64_t cap) {
+// Workgroups for at most n messages of at most max_msg_bytes each, plus
+// `extra` chunks that cutting the messages up may add.
+static uint32_t vl_grid(uint32_t n, uint64_t max_msg_bytes, uint64_t extra,
+                        uint64_t waves, uint64_t cap) {
   if (!cap) cap = 1;
   if (!max_msg_bytes) return (uint32_t)cap;
   uint64_t bound;
   if (__builtin_mul_overflow(rocp2p_vl_chunks(max_msg_bytes), (uint64_t)n,
-                             &bound))
+                             &bound) ||
+      __builtin_add_overflow(bound, extra, &bound))
     return (uint32_t)cap;
   uint64_t blocks = bound / waves + (bound % waves != 0);
   return (uint32_t)(blocks > cap ? cap : blocks);  // >= 1: n, max > 0
@@ -1940,39 +1990,17 @@ static hipError_t msg_engine_v_launch(void* region, const uint64_t* d_offs,
                                       uint32_t grid_cap, hipStream_t stream) {
   if (!d_cstart || (uintptr_t)region % 16) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
-  hipError_t e;
-  uint64_t cap = gather_grid_cap();
-  if (d_out) {
-    e = crc_tables_ready();
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-  }
-  // The fused form keeps k_msg_engine_crc's 128 workgroups.  The plain
-  // gather has the same four 16-byte PCIe reads per lane in flight and,
-  // measured on MI355X, the same optimum (4 KiB and 1 MiB messages:
-  // 53.0 GB/s at 512 workgroups, 53.5 at 256, 56.1-56.7 at 128 and 64);
-  // only batches known to hold sub-chunk messages, whose waves have few
-  // lanes busy, do better with the full cap (64 B: 19.6 GB/s at 128,
-  // 22.4 at 512).  The plain scatter does not care from 4 KiB up and
-  // wants the full cap at 64 B (21.5 at 128, 26.1 at 512).
-  const bool small = max_msg_bytes && max_msg_bytes < PAGE;
-  if ((d_out || (GATHER && !small)) && cap > ICRC_GRID) cap = ICRC_GRID;
-  if (grid_cap && grid_cap < cap) cap = grid_cap;
+  hipError_t e = d_out ? crc_out_ready(d_out, n, stream) : hipSuccess;
+  if (e != hipSuccess) return e;
   e = vl_scan_launch(d_lens, n, d_cstart, stream);
   if (e != hipSuccess) return e;
-  const uint32_t grid = vl_grid(n, max_msg_bytes, ICRC_WAVES, cap);
-  if (d_out)
-    hipLaunchKernelGGL((k_msg_engine_v<GATHER, true>), dim3(grid),
-                       dim3(WAVE * ICRC_WAVES), 0, stream, (uint8_t*)region,
-                       d_offs, d_addrs, d_lens, (const uint64_t*)d_cstart, n,
-                       d_out);
-  else
-    hipLaunchKernelGGL((k_msg_engine_v<GATHER, false>), dim3(grid),
-                       dim3(WAVE * ICRC_WAVES), 0, stream, (uint8_t*)region,
-                       d_offs, d_addrs, d_lens, (const uint64_t*)d_cstart, n,
-                       d_out);
-  return hipGetLastError();
+  const uint64_t cap =
+      engine_grid_cap(GATHER, d_out != nullptr, max_msg_bytes, grid_cap);
+  const uint32_t grid = vl_grid(n, max_msg_bytes, 0, ICRC_WAVES, cap);
+  return engine_launch(k_msg_engine_v<GATHER, true>,
+                       k_msg_engine_v<GATHER, false>, d_out, grid, stream,
+                       (uint8_t*)region, d_offs, d_addrs, d_lens,
+                       (const uint64_t*)d_cstart, n);
 }
 
 extern "C" hipError_t rocp2p_gather_v(void* dst_base,
@@ -2010,14 +2038,12 @@ extern "C" hipError_t rocp2p_crc32_msgs_v(const void* base,
                                           hipStream_t stream) {
   if (!d_cstart || (uintptr_t)base % 16) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
-  hipError_t e = crc_tables_ready();
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+  hipError_t e = crc_out_ready(d_out, n, stream);
   if (e != hipSuccess) return e;
   e = vl_scan_launch(d_lens, n, d_cstart, stream);
   if (e != hipSuccess) return e;
-  const uint32_t grid =
-      vl_grid(n, max_msg_bytes, CRC_DIGEST_WAVES, grid_cap ? grid_cap : 256);
+  const uint32_t grid = vl_grid(n, max_msg_bytes, 0, CRC_DIGEST_WAVES,
+                                digest_grid_cap(grid_cap));
   hipLaunchKernelGGL(k_crc32_msgs_v, dim3(grid),
                      dim3(WAVE * CRC_DIGEST_WAVES), 0, stream,
                      (const uint8_t*)base, d_offs, d_lens,
@@ -2029,9 +2055,7 @@ extern "C" hipError_t rocp2p_crc32_msgs_v(const void* base,
 // Byte-granular launchers: those of the variable-length forms with
 // k_vl_scan_b over the side that is written.  A skewed message of
 // max_msg_bytes may have one chunk more than an aligned one (b_bound);
-// like max_msg_bytes itself that only sizes the grid.  The grid caps are
-// msg_engine_v_launch's until measurements say otherwise
-// (docs/PERF.md).
+// like max_msg_bytes itself that only sizes the grid.
 
 static uint64_t b_bound(uint64_t max_msg_bytes) {
   return max_msg_bytes ? max_msg_bytes + PAGE : 0;
@@ -2054,33 +2078,20 @@ static hipError_t msg_engine_b_launch(void* region, const uint64_t* d_offs,
                                       uint32_t grid_cap, hipStream_t stream) {
   if (!d_cstart || (uintptr_t)region % 16) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
-  hipError_t e;
-  uint64_t cap = gather_grid_cap();
-  if (d_out) {
-    e = crc_tables_ready();
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-  }
-  const bool small = max_msg_bytes && max_msg_bytes < PAGE;
-  if ((d_out || (GATHER && !small)) && cap > ICRC_GRID) cap = ICRC_GRID;
-  if (grid_cap && grid_cap < cap) cap = grid_cap;
+  hipError_t e = d_out ? crc_out_ready(d_out, n, stream) : hipSuccess;
+  if (e != hipSuccess) return e;
   // the region base is 16-byte aligned: an offset's low bits are the skew
   e = vl_scan_b_launch(d_lens, GATHER ? d_offs : d_addrs, n, d_cstart,
                        stream);
   if (e != hipSuccess) return e;
-  const uint32_t grid = vl_grid(n, b_bound(max_msg_bytes), ICRC_WAVES, cap);
-  if (d_out)
-    hipLaunchKernelGGL((k_msg_engine_b<GATHER, true>), dim3(grid),
-                       dim3(WAVE * ICRC_WAVES), 0, stream, (uint8_t*)region,
-                       d_offs, d_addrs, d_lens, (const uint64_t*)d_cstart, n,
-                       d_out);
-  else
-    hipLaunchKernelGGL((k_msg_engine_b<GATHER, false>), dim3(grid),
-                       dim3(WAVE * ICRC_WAVES), 0, stream, (uint8_t*)region,
-                       d_offs, d_addrs, d_lens, (const uint64_t*)d_cstart, n,
-                       d_out);
-  return hipGetLastError();
+  const uint64_t cap =
+      engine_grid_cap(GATHER, d_out != nullptr, max_msg_bytes, grid_cap);
+  const uint32_t grid =
+      vl_grid(n, b_bound(max_msg_bytes), 0, ICRC_WAVES, cap);
+  return engine_launch(k_msg_engine_b<GATHER, true>,
+                       k_msg_engine_b<GATHER, false>, d_out, grid, stream,
+                       (uint8_t*)region, d_offs, d_addrs, d_lens,
+                       (const uint64_t*)d_cstart, n);
 }
 
 extern "C" hipError_t rocp2p_gather_b(void* dst_base,
@@ -2118,14 +2129,12 @@ extern "C" hipError_t rocp2p_crc32_msgs_b(const void* base,
                                           hipStream_t stream) {
   if (!d_cstart || (uintptr_t)base % 16) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
-  hipError_t e = crc_tables_ready();
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
+  hipError_t e = crc_out_ready(d_out, n, stream);
   if (e != hipSuccess) return e;
   e = vl_scan_b_launch(d_lens, d_offs, n, d_cstart, stream);
   if (e != hipSuccess) return e;
-  const uint32_t grid = vl_grid(n, b_bound(max_msg_bytes), CRC_DIGEST_WAVES,
-                                grid_cap ? grid_cap : 256);
+  const uint32_t grid = vl_grid(n, b_bound(max_msg_bytes), 0,
+                                CRC_DIGEST_WAVES, digest_grid_cap(grid_cap));
   hipLaunchKernelGGL(k_crc32_msgs_b, dim3(grid),
                      dim3(WAVE * CRC_DIGEST_WAVES), 0, stream,
                      (const uint8_t*)base, d_offs, d_lens,
@@ -2137,21 +2146,7 @@ extern "C" hipError_t rocp2p_crc32_msgs_b(const void* base,
 // Scatter/gather launchers: the scan, then the engine, on one stream.
 // max_msg_bytes bounds a whole message; cut into its SGEs a message has
 // at most two chunks more per SGE than the bytes alone would give (a
-// partial first and a partial last one).  That only sizes the grid.  The
-// grid caps are msg_engine_b_launch's.
-
-static uint32_t sg_grid(uint32_t n, uint32_t nsge, uint64_t max_msg_bytes,
-                        uint64_t cap) {
-  if (!cap) cap = 1;
-  if (!max_msg_bytes) return (uint32_t)cap;
-  uint64_t bound;
-  if (__builtin_mul_overflow(rocp2p_vl_chunks(max_msg_bytes), (uint64_t)n,
-                             &bound) ||
-      __builtin_add_overflow(bound, 2 * (uint64_t)nsge, &bound))
-    return (uint32_t)cap;
-  uint64_t blocks = bound / ICRC_WAVES + (bound % ICRC_WAVES != 0);
-  return (uint32_t)(blocks > cap ? cap : blocks);  // >= 1: nsge > 0
-}
+// partial first and a partial last one).  That only sizes the grid.
 
 template <bool GATHER>
 static hipError_t msg_engine_sg_launch(void* region, const uint64_t* d_offs,
@@ -2164,38 +2159,24 @@ static hipError_t msg_engine_sg_launch(void* region, const uint64_t* d_offs,
                                        hipStream_t stream) {
   if (!d_scratch || (uintptr_t)region % 16) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
-  hipError_t e;
-  uint64_t cap = gather_grid_cap();
-  if (d_out) {
-    e = crc_tables_ready();
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-  }
+  hipError_t e = d_out ? crc_out_ready(d_out, n, stream) : hipSuccess;
+  if (e != hipSuccess) return e;
   if (!nsge) return hipSuccess;  // n messages without a byte
-  const bool small = max_msg_bytes && max_msg_bytes < PAGE;
-  if ((d_out || (GATHER && !small)) && cap > ICRC_GRID) cap = ICRC_GRID;
-  if (grid_cap && grid_cap < cap) cap = grid_cap;
   hipLaunchKernelGGL(k_sg_scan<GATHER>, dim3(1), dim3(VL_SCAN_THREADS), 0,
                      stream, (const uint8_t*)region, d_offs, d_sge_start,
                      d_sge_addrs, d_sge_lens, n, nsge, d_scratch);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const rocp2p_sgl_view v = rocp2p_sgl_carve(d_scratch, nsge);
-  const uint32_t grid = sg_grid(n, nsge, max_msg_bytes, cap);
-  if (d_out)
-    hipLaunchKernelGGL(k_msg_engine_sg<true>, dim3(grid),
-                       dim3(WAVE * ICRC_WAVES), 0, stream, d_sge_lens,
-                       (const uint64_t*)v.cstart, (const uint64_t*)v.to,
-                       (const uint64_t*)v.from, (const uint64_t*)v.tail,
-                       (const uint32_t*)v.owner, nsge, d_out);
-  else
-    hipLaunchKernelGGL(k_msg_engine_sg<false>, dim3(grid),
-                       dim3(WAVE * ICRC_WAVES), 0, stream, d_sge_lens,
-                       (const uint64_t*)v.cstart, (const uint64_t*)v.to,
-                       (const uint64_t*)v.from, (const uint64_t*)v.tail,
-                       (const uint32_t*)v.owner, nsge, d_out);
-  return hipGetLastError();
+  const uint64_t cap =
+      engine_grid_cap(GATHER, d_out != nullptr, max_msg_bytes, grid_cap);
+  const uint32_t grid =
+      vl_grid(n, max_msg_bytes, 2 * (uint64_t)nsge, ICRC_WAVES, cap);
+  return engine_launch(k_msg_engine_sg<true>, k_msg_engine_sg<false>, d_out,
+                       grid, stream, d_sge_lens, (const uint64_t*)v.cstart,
+                       (const uint64_t*)v.to, (const uint64_t*)v.from,
+                       (const uint64_t*)v.tail, (const uint32_t*)v.owner,
+                       nsge);
 }
 
 extern "C" hipError_t rocp2p_gather_sg(
