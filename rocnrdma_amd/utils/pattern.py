@@ -90,6 +90,43 @@ def crc32_combine(c1: int, c2: int, len2: int) -> int:
     return crc32_shift(c1, len2) ^ (c2 & 0xFFFFFFFF)
 
 
+def crc32_repeat(crc: int, nbytes: int, times: int) -> int:
+    """crc(X * times) from crc = crc(X) and nbytes = len(X), by
+    square-and-multiply over crc32_combine (times >= 0)."""
+    if times < 0 or nbytes < 0:
+        raise ValueError("negative count")
+    out = 0  # crc of the empty string
+    while times:
+        if times & 1:
+            out = crc32_combine(out, crc, nbytes)
+        crc = crc32_combine(crc, crc, nbytes)
+        nbytes *= 2
+        times >>= 1
+    return out
+
+
+def crc32_periodic_reference(block: bytes | np.ndarray, start: int,
+                             length: int) -> int:
+    """zlib.crc32 of the `length` bytes from byte `start` of the endless
+    repetition of `block`, without materialising them: zlib on one whole
+    block rotated to the phase of `start` and on one partial block,
+    joined with crc32_repeat / crc32_combine.  Exact for any length below
+    2**64; the GPU tests' reference for multi-GiB periodic buffers."""
+    blk = np.asarray(block, dtype=np.uint8).tobytes()
+    period = len(blk)
+    if period == 0 or start < 0 or length < 0:
+        raise ValueError("empty block or negative range")
+    phase = start % period
+    whole, rest = divmod(length, period)
+
+    def take(n):  # the n <= period bytes from the phase on
+        head = blk[phase : phase + n]
+        return head + blk[: n - len(head)]
+
+    crc = crc32_repeat(zlib.crc32(take(period)), period, whole) if whole else 0
+    return crc32_combine(crc, zlib.crc32(take(rest)), rest)
+
+
 def crc32_messages_reference(data: bytes | np.ndarray, msg_bytes: int,
                              offs=None) -> np.ndarray:
     """zlib.crc32 of each msg_bytes message, as uint32 array: message m

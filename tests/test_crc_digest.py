@@ -186,7 +186,23 @@ static_assert(T.slice[0][1] == 0x77073096u, "slice-by-8 table");
 static_assert(T.xpow8[0][1] == 0x00800000u, "byte-sliced power table");
 static_assert(T.shift[0][3][0x80] == 0x88d14467u, "shift operators");
 
-int main() {
+// "combine" mode: zlib's own crc32_combine64 at fixed inputs, one line
+// "c1 c2 len2 result" each, for the Python combine to be compared with.
+static int print_combines() {
+  const uint64_t lens[] = {(1ull << 24) + 5, (1ull << 32) + 28688,
+                           (1ull << 33) + 5};
+  const uint32_t cs[][2] = {{0x00000001u, 0u},          {0x80000000u, 0u},
+                            {0xCBF43926u, 0u},          {0xCBF43926u, 0xDEADBEEFu},
+                            {0xFFFFFFFFu, 0x12345678u}, {0x0BADF00Du, 0xFFFFFFFFu}};
+  for (uint64_t n : lens)
+    for (const auto& c : cs)
+      std::printf("%u %u %llu %u\n", c[0], c[1], (unsigned long long)n,
+                  (uint32_t)crc32_combine64(c[0], c[1], (z_off64_t)n));
+  return 0;
+}
+
+int main(int argc, char**) {
+  if (argc > 1) return print_combines();
   uint32_t tab[ROCP2P_CRC_XPOW_N];
   rocp2p_crc_xpow_table(tab);
   CHECK(tab[0] == 0x00800000u);
@@ -257,8 +273,7 @@ int main() {
 """
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_crc_header_against_zlib(tmp_path):
+def _build_header_prog(tmp_path):
     src = tmp_path / "crc_header_check.cpp"
     exe = tmp_path / "crc_header_check"
     src.write_text(_HEADER_PROG)
@@ -269,6 +284,61 @@ def test_crc_header_against_zlib(tmp_path):
          "-I", os.path.join(ROOT, "rocnrdma_amd", "ops", "csrc"),
          str(src), "-lz", "-o", str(exe)],
         check=True, capture_output=True, text=True)
+    return exe
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_crc_header_against_zlib(tmp_path):
+    exe = _build_header_prog(tmp_path)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.strip() == "OK"
+
+
+# -- lengths past 4 GiB, and the periodic reference of the wide GPU tier ---
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_python_combine_matches_zlib_combine64_past_4gib(tmp_path):
+    """pattern.crc32_combine / crc32_shift at second-part lengths that do
+    not fit in memory, against zlib's crc32_combine64 (printed by the C
+    program above for fixed inputs)."""
+    exe = _build_header_prog(tmp_path)
+    r = subprocess.run([str(exe), "combine"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rows = [tuple(int(x) for x in ln.split()) for ln in r.stdout.splitlines()]
+    assert len(rows) == 18
+    assert {n for _, _, n, _ in rows} == {2 ** 24 + 5, 2 ** 32 + 28688,
+                                          2 ** 33 + 5}
+    for c1, c2, n, want in rows:
+        assert pattern.crc32_combine(c1, c2, n) == want
+        if c2 == 0:
+            assert pattern.crc32_shift(c1, n) == want
+
+
+def test_repeat_matches_zlib(blob):
+    for n in (0, 1, 17, 1000):
+        for times in (0, 1, 2, 3, 7, 16, 33):
+            x = blob[100:100 + n]
+            assert pattern.crc32_repeat(zlib.crc32(x), n, times) == zlib.crc32(
+                x * times)
+
+
+@pytest.mark.parametrize("period", [1, 48, 1009])
+def test_periodic_reference_matches_materialised_bytes(blob, period):
+    """crc32_periodic_reference against plain zlib on the bytes themselves:
+    ranges inside one period, across one boundary, and over one and
+    several whole periods, from every kind of phase."""
+    block = np.frombuffer(blob[:period], dtype=np.uint8)
+    stream = blob[:period] * 16
+    pairs = [(s, n) for s in (0, 1, period - 1, period, period + 5,
+                              3 * period + period // 2)
+             for n in (0, 1, period - 1, period, period + 1, 2 * period,
+                       5 * period + 3, 7 * period)]
+    assert len(pairs) == 48
+    for s, n in pairs:
+        assert s + n <= len(stream)
+        assert pattern.crc32_periodic_reference(block, s, n) == zlib.crc32(
+            stream[s:s + n]), (s, n)
+    with pytest.raises(ValueError):
+        pattern.crc32_periodic_reference(block[:0], 0, 1)
+    with pytest.raises(ValueError):
+        pattern.crc32_periodic_reference(block, -1, 1)
