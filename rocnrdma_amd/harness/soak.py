@@ -5,7 +5,7 @@ deploy candidate; the GPU test tier runs a short bounded pass).
 
 CLI: python -m rocnrdma_amd.harness.soak [--secs 30] [--transport auto]
                                          [--audit pattern|crc] [--mixed]
-                                         [--bytes] [--sg K]
+                                         [--bytes] [--sg K] [--prot]
 Exit nonzero on any integrity failure.
 """
 from __future__ import annotations
@@ -80,7 +80,8 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
              region_bytes: int = 256 << 20, seed: int = 1234,
              device=None, metrics=None, audit: str = "pattern",
              icrc: bool = False, mixed: bool = False,
-             byte_granular: bool = False, sg: int = 0) -> dict:
+             byte_granular: bool = False, sg: int = 0,
+             prot: bool = False) -> dict:
     """audit="pattern": splitmix64 pattern + integrity_check (default).
     audit="crc": a seeded random payload per cycle through digest_check
     (per-message CRC32, content-independent).
@@ -99,7 +100,16 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
     sg=K > 1 (needs byte_granular): the transport is opened with
     max_sge=K and staging_skew 0, every post carries a seeded
     scatter/gather list (mixed_sges) and the audit is
-    digest_check_sg(payload, sges)."""
+    digest_check_sg(payload, sges).
+    prot=True (needs byte_granular, not sg): the transport is opened with
+    protected=True; every cycle registers a seeded window MR and posts
+    bursts in which a seeded minority of the messages use the window key
+    outside its range, a deregistered key or a key without the needed
+    right.  completions() is compared with the model
+    (utils.prot.prot_reference), rejected and flushed messages must have
+    left the known byte in place and accepted ones must have landed;
+    reset_qp() runs between bursts and the audit follows with the
+    default keys."""
     from rocnrdma_amd.harness.sweep import pattern_sender
     from rocnrdma_amd.transport import get_transport
 
@@ -112,6 +122,10 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
         raise ValueError("sg must be 0 (off) or a max_sge of at least 2")
     if sg and not byte_granular:
         raise ValueError("sg needs mixed=True and byte_granular=True")
+
+    if prot and (not byte_granular or sg):
+        raise ValueError("prot needs mixed=True and byte_granular=True, "
+                         "and no sg")
 
     if metrics is None:
         from rocnrdma_amd.utils.metrics import TransferMetrics
@@ -127,6 +141,9 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
         stats.update(icrc_checked=0, icrc_bad=0)
     if mixed:
         extra["var_len"] = True
+    if prot:
+        extra["protected"] = True
+        stats.update(prot_rejected=0, prot_flushed=0)
     while time.monotonic() < t_end:
         msg = rng.choice(SIZES)
         direction = rng.choice(["write", "read"])
@@ -140,7 +157,10 @@ def run_soak(transport: str = "auto", secs: float = 10.0,
                            direction=direction, device=device, **extra)
         try:
             if mixed:
-                moved, msgs, bad = _mixed_cycle(tp, rng, region)
+                if prot:
+                    moved, msgs, bad = _prot_cycle(tp, rng, region, stats)
+                else:
+                    moved, msgs, bad = _mixed_cycle(tp, rng, region)
                 stats["audits"] += 1
                 if bad:
                     stats["failures"] += 1
@@ -215,6 +235,107 @@ def _mixed_cycle(tp, rng: random.Random, region: int):
     return (moved + int(lens.sum()), posted + tp.msgs_per_region, bad)
 
 
+_PROT_KNOWN = 0x3C  # what a receiver holds before a protected burst
+
+
+def _prot_cycle(tp, rng: random.Random, region: int, stats: dict):
+    """One cycle of hostile traffic on an open protected transport:
+    (bytes moved, messages moved, bad messages).  Bad: a completion that
+    differs from the model's, a rejected or flushed message whose
+    receiver lost the known byte, an accepted one that did not land, and
+    whatever the closing audit finds."""
+    import numpy as np
+
+    from rocnrdma_amd.utils import prot as P
+
+    msg, mpr, inflight = tp.msg_bytes, tp.msgs_per_region, tp.inflight
+    rs, ss = tp.region_skew, tp.staging_skew
+    write = tp.direction == "write"
+    on_gpu = hasattr(tp, "staging_flat")
+    if on_gpu:
+        import torch
+
+        staging = tp.staging_flat.numpy().reshape(inflight, msg)
+    else:
+        staging = tp.staging
+
+    def region_get():
+        return tp.region.cpu().numpy() if on_gpu else tp.region
+
+    def region_set(arr):
+        if on_gpu:
+            tp.region.copy_(torch.from_numpy(arr))
+            torch.cuda.synchronize(tp.device)
+        else:
+            tp.region[:] = arr
+
+    g = np.random.default_rng(rng.getrandbits(32))
+    # the window: a run of whole region messages, every right granted
+    w0 = rng.randrange(mpr)
+    w1 = rng.randint(w0 + 1, mpr)
+    window = tp.reg_mr("region", w0 * msg, (w1 - w0) * msg,
+                       P.ACCESS_REMOTE_READ | P.ACCESS_REMOTE_WRITE)
+    weak = tp.reg_mr("region", 0, region,  # the right this direction lacks
+                     P.ACCESS_REMOTE_READ if write else P.ACCESS_REMOTE_WRITE)
+    stale = tp.reg_mr("region", 0, region,
+                      P.ACCESS_REMOTE_READ | P.ACCESS_REMOTE_WRITE)
+    tp.dereg_mr(stale)
+    moved = posted = bad = 0
+    for _ in range(rng.randint(1, 4)):
+        burst = min(rng.randint(1, max(2, inflight)), inflight)
+        lens = mixed_lens(rng, burst, tp.max_nbytes, 1)
+        idx = np.arange(posted, posted + burst)
+        rkeys = np.full(burst, tp.region_key, dtype=np.int64)
+        hostile = g.random(burst) < min(0.25, 2.0 / burst)
+        rkeys[hostile] = g.choice([window, weak, stale], int(hostile.sum()))
+        friendly = ~hostile & (g.random(burst) < 0.3)
+        rkeys[friendly] = window  # in range or not: the model knows
+        # sender random, receiver known
+        data = g.integers(0, 256, (burst, msg), dtype=np.uint8)
+        reg = np.full(region, _PROT_KNOWN, dtype=np.uint8)
+        slots, rmsg = idx % inflight, idx % mpr
+        if write:
+            staging[slots] = data
+        else:
+            staging[slots] = _PROT_KNOWN
+            for k in range(burst):
+                reg[rmsg[k] * msg:(rmsg[k] + 1) * msg] = data[k]
+        region_set(reg)
+        want, elens, _ = tp.prot_expected(posted, burst, lens, rkey=rkeys)
+        tp.post_many(posted, burst, lens, rkey=rkeys)
+        tp.flush()
+        got = tp.completions()
+        mism = np.zeros(burst, dtype=bool)
+        if got.shape != want.shape:
+            mism[:] = True
+        else:
+            mism |= got != want
+        reg = region_get()
+        for k in range(burst):
+            ln = int(elens[k])
+            there = reg[rmsg[k] * msg:(rmsg[k] + 1) * msg]
+            slot = staging[slots[k]]
+            recv, sent = ((there, slot[ss:ss + ln]) if write
+                          else (slot, there[rs:rs + ln]))
+            at = rs if write else ss
+            mism[k] |= bool((recv[:at] != _PROT_KNOWN).any() or
+                            (recv[at:at + ln] != sent).any() or
+                            (recv[at + ln:] != _PROT_KNOWN).any())
+        bad += int(mism.sum())
+        stats["prot_rejected"] += int(
+            ((want != P.WC_SUCCESS) & (want != P.WC_WR_FLUSH_ERR)).sum())
+        stats["prot_flushed"] += int((want == P.WC_WR_FLUSH_ERR).sum())
+        moved += int(elens.sum())
+        posted += burst
+        tp.reset_qp()
+    tp.dereg_mr(window)
+    tp.dereg_mr(weak)
+    payload = g.integers(0, 256, region, dtype=np.uint8)
+    lens = mixed_lens(rng, mpr, tp.max_nbytes, 1)
+    bad += tp.digest_check(payload, lens)
+    return (moved + int(lens.sum()), posted + mpr, bad)
+
+
 def _sg_cycle(tp, rng: random.Random, region: int):
     """_mixed_cycle with a seeded scatter/gather list per message."""
     import numpy as np
@@ -264,6 +385,11 @@ def main():
                     help="with --mixed --bytes: scatter/gather traffic, "
                          "up to K SGEs per message in seeded layouts, "
                          "audited with digest_check_sg")
+    ap.add_argument("--prot", action="store_true",
+                    help="with --mixed --bytes: protected traffic, a "
+                         "seeded minority of the messages with keys that "
+                         "must be rejected; completions are compared with "
+                         "the model and rejected messages must move nothing")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="expose Prometheus metrics on this port")
     args = ap.parse_args()
@@ -273,7 +399,8 @@ def main():
     stats = run_soak(args.transport, args.secs, args.region_bytes,
                      args.seed, metrics=metrics, audit=args.audit,
                      icrc=args.icrc, mixed=args.mixed,
-                     byte_granular=args.byte_granular, sg=args.sg)
+                     byte_granular=args.byte_granular, sg=args.sg,
+                     prot=args.prot)
     print(stats)
     raise SystemExit(1 if stats["failures"] else 0)
 

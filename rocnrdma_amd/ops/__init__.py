@@ -220,6 +220,66 @@ def scatter_sg_(region: torch.Tensor, offs: torch.Tensor,
     return _require().scatter_sg_(region, offs, sge_start, sge_addrs,
                                   sge_lens, max_msg_bytes, crc, grid_cap)
 
+# enum ibv_wc_status, as far as the protected engines produce it, and the
+# verbs access bits of an MR-table entry
+WC_SUCCESS = 0
+WC_LOC_LEN_ERR = 1
+WC_LOC_PROT_ERR = 4
+WC_WR_FLUSH_ERR = 5
+WC_REM_ACCESS_ERR = 10
+ACCESS_LOCAL_WRITE = 1
+ACCESS_REMOTE_WRITE = 2
+ACCESS_REMOTE_READ = 4
+
+
+def gather_prot_(region: torch.Tensor, dst_offs: torch.Tensor,
+                 src_addrs: torch.Tensor, lens: torch.Tensor,
+                 keys: torch.Tensor, mrs: torch.Tensor, *,
+                 qp_state: torch.Tensor | None = None,
+                 max_msg_bytes: int = 0, crc: bool = False,
+                 grid_cap: int = 0):
+    """gather_bytes_ behind memory protection, as an HCA checks a work
+    request before it moves a byte.  keys[m] = lkey << 32 | rkey (int64
+    [n], utils.prot.pack_keys); mrs is the MR table, contiguous int64
+    [R, 4] on the region's device with rows (key, addr, length, access):
+    a key is slot << 8 | tag and must sit in row `slot` with access != 0,
+    access holds the ACCESS_* bits.  Per message, first rule wins: lens
+    == 0 -> WC_SUCCESS (keys not read); lens < 0 -> WC_LOC_LEN_ERR; the
+    outside range [src_addrs, +lens) not inside the MR of lkey ->
+    WC_LOC_PROT_ERR; the region range [region + dst_offs, +lens) not
+    inside the MR of rkey, or that MR without ACCESS_REMOTE_WRITE ->
+    WC_REM_ACCESS_ERR.  No descriptor value is trusted: a message that
+    does not complete with WC_SUCCESS moves nothing and its digest is 0.
+
+    qp_state (int32 [1] on the device, 0 = ready) orders the batch like a
+    queue pair: the first failing message completes with its own status,
+    every later one with WC_WR_FLUSH_ERR, and the word is set to 1; a
+    word that is non-zero on entry flushes the whole batch.  Without it
+    every message is judged on its own.
+
+    Returns (status, digests): int32 [n] each, digests None unless
+    crc=True; no sync.  With a table that covers everything, valid keys
+    and qp_state=None the bytes and digests are bit for bit those of
+    gather_bytes_ and every status is 0.  max_msg_bytes and grid_cap as
+    for gather_bytes_."""
+    return _require().gather_prot_(region, dst_offs, src_addrs, lens, keys,
+                                   mrs, qp_state, max_msg_bytes, crc,
+                                   grid_cap)
+
+
+def scatter_prot_(region: torch.Tensor, src_offs: torch.Tensor,
+                  dst_addrs: torch.Tensor, lens: torch.Tensor,
+                  keys: torch.Tensor, mrs: torch.Tensor, *,
+                  qp_state: torch.Tensor | None = None,
+                  max_msg_bytes: int = 0, crc: bool = False,
+                  grid_cap: int = 0):
+    """scatter_bytes_ behind memory protection; see gather_prot_.  The
+    outside MR (lkey) is written and needs ACCESS_LOCAL_WRITE, the region
+    MR (rkey) is read and needs ACCESS_REMOTE_READ."""
+    return _require().scatter_prot_(region, src_offs, dst_addrs, lens, keys,
+                                    mrs, qp_state, max_msg_bytes, crc,
+                                    grid_cap)
+
 
 def dmabuf_fd(buf: torch.Tensor) -> int:
     """Export an HBM tensor as a dmabuf fd (ibv_reg_dmabuf_mr's GPU

@@ -10,6 +10,7 @@
 
 #include "p2p_kernels.h"
 #include "p2p_sgl.h"  // ROCP2P_SGL_SCRATCH_WORDS
+#include "p2p_prot.h"  // ROCP2P_PROT_SCRATCH_WORDS
 
 namespace {
 
@@ -388,6 +389,85 @@ c10::optional<torch::Tensor> scatter_sg_(torch::Tensor region,
                        grid_cap);
 }
 
+// The protected forms (p2p_prot.h): the checks of gather_bytes_, the key
+// row, the MR table and the optional queue-pair word — every
+// host-visible argument error raises before anything is launched.
+// Status, scratch and digests are torch tensors like the _v forms'.
+template <typename Launch>
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> msg_engine_prot(
+    const char* who, Launch launch, torch::Tensor region, torch::Tensor offs,
+    torch::Tensor addrs, torch::Tensor lens, torch::Tensor keys,
+    torch::Tensor mrs, c10::optional<torch::Tensor> qp_state,
+    int64_t max_msg_bytes, bool crc, int64_t grid_cap) {
+  OnDeviceOf dev(region, who);
+  check_align16(region, who);
+  for (const torch::Tensor* t : {&offs, &addrs, &lens, &keys, &mrs}) {
+    check_u64_dev(*t, who);
+    TORCH_CHECK(t->device() == region.device(), who,
+                ": descriptors must live on the region's device");
+  }
+  const int64_t n = offs.numel();
+  TORCH_CHECK(addrs.numel() == n && lens.numel() == n && keys.numel() == n,
+              who, ": n mismatch");
+  TORCH_CHECK(n < (1LL << 32), who, ": too many messages");
+  TORCH_CHECK(mrs.dim() == 2 && mrs.size(1) == ROCP2P_PROT_MR_WORDS, who,
+              ": mrs must have shape [R, 4] (key, addr, length, access)");
+  TORCH_CHECK(mrs.size(0) >= 1 && mrs.size(0) <= (int64_t)ROCP2P_PROT_MAX_MR,
+              who, ": mrs must have between 1 and 2^20 entries");
+  int32_t* d_qp = nullptr;
+  if (qp_state.has_value()) {
+    TORCH_CHECK(qp_state->is_cuda() && qp_state->is_contiguous() &&
+                    qp_state->scalar_type() == torch::kInt32 &&
+                    qp_state->dim() == 1 && qp_state->numel() == 1,
+                who, ": qp_state must be an int32 tensor of shape [1] on GPU");
+    TORCH_CHECK(qp_state->device() == region.device(), who,
+                ": qp_state must live on the region's device");
+    d_qp = qp_state->data_ptr<int32_t>();
+  }
+  TORCH_CHECK(max_msg_bytes >= 0, who, ": max_msg_bytes out of range");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= 0xffffffffLL, who,
+              ": grid_cap out of range");
+  auto i32 = torch::dtype(torch::kInt32).device(region.device());
+  auto status = torch::empty({n}, i32);
+  auto scratch = torch::empty(
+      {(int64_t)ROCP2P_PROT_SCRATCH_WORDS(n)},
+      torch::dtype(torch::kInt64).device(region.device()));
+  c10::optional<torch::Tensor> out;
+  if (crc) out = torch::empty({n}, i32);
+  if (!n) return {status, out};  // nothing to judge; the word stays
+  HIP_OK(launch(region.data_ptr(), (const uint64_t*)offs.data_ptr<int64_t>(),
+                (const uint64_t*)addrs.data_ptr<int64_t>(),
+                (const uint64_t*)lens.data_ptr<int64_t>(),
+                (const uint64_t*)keys.data_ptr<int64_t>(), (uint32_t)n,
+                (const uint64_t*)mrs.data_ptr<int64_t>(),
+                (uint32_t)mrs.size(0), d_qp, (uint64_t)max_msg_bytes,
+                (uint64_t*)scratch.data_ptr<int64_t>(),
+                status.data_ptr<int32_t>(),
+                crc ? (uint32_t*)out->data_ptr<int32_t>() : nullptr,
+                (uint32_t)grid_cap, dev.stream));
+  return {status, out};
+}
+
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> gather_prot_(
+    torch::Tensor region, torch::Tensor dst_offs, torch::Tensor src_addrs,
+    torch::Tensor lens, torch::Tensor keys, torch::Tensor mrs,
+    c10::optional<torch::Tensor> qp_state, int64_t max_msg_bytes, bool crc,
+    int64_t grid_cap) {
+  return msg_engine_prot("gather_prot_", rocp2p_gather_p, region, dst_offs,
+                         src_addrs, lens, keys, mrs, qp_state, max_msg_bytes,
+                         crc, grid_cap);
+}
+
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> scatter_prot_(
+    torch::Tensor region, torch::Tensor src_offs, torch::Tensor dst_addrs,
+    torch::Tensor lens, torch::Tensor keys, torch::Tensor mrs,
+    c10::optional<torch::Tensor> qp_state, int64_t max_msg_bytes, bool crc,
+    int64_t grid_cap) {
+  return msg_engine_prot("scatter_prot_", rocp2p_scatter_p, region, src_offs,
+                         dst_addrs, lens, keys, mrs, qp_state, max_msg_bytes,
+                         crc, grid_cap);
+}
+
 void copy_(torch::Tensor dst, torch::Tensor src) {
   OnDeviceOf dev(dst, "copy_");
   check_buf(src, "copy_");
@@ -487,6 +567,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sge_addrs"), py::arg("sge_lens"),
         py::arg("max_msg_bytes") = 0, py::arg("crc") = false,
         py::arg("grid_cap") = 0);
+  m.def("gather_prot_", &gather_prot_,
+        "gather_bytes_ behind MR keys, bounds and access checks; returns "
+        "(status, digests or None)",
+        py::arg("region"), py::arg("dst_offs"), py::arg("src_addrs"),
+        py::arg("lens"), py::arg("keys"), py::arg("mrs"),
+        py::arg("qp_state") = py::none(), py::arg("max_msg_bytes") = 0,
+        py::arg("crc") = false, py::arg("grid_cap") = 0);
+  m.def("scatter_prot_", &scatter_prot_,
+        "scatter_bytes_ behind MR keys, bounds and access checks; returns "
+        "(status, digests or None)",
+        py::arg("region"), py::arg("src_offs"), py::arg("dst_addrs"),
+        py::arg("lens"), py::arg("keys"), py::arg("mrs"),
+        py::arg("qp_state") = py::none(), py::arg("max_msg_bytes") = 0,
+        py::arg("crc") = false, py::arg("grid_cap") = 0);
   m.def("dmabuf_fd", &dmabuf_fd,
         "export an HBM tensor range as a dmabuf fd (caller closes)");
 }

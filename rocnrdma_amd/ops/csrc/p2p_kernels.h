@@ -210,4 +210,42 @@ hipError_t rocp2p_scatter_sg(const void* src_base, const uint64_t* d_src_offs,
                              uint64_t* d_scratch, uint32_t* d_out,
                              uint32_t grid_cap, hipStream_t stream);
 
+// Memory protection for the byte-granular engine (rules: p2p_prot.h).
+// The descriptors of the _b calls plus d_keys[m] = lkey << 32 | rkey and
+// an MR table d_mrs of nmr entries {key, addr, length, access} (device,
+// 4 words each).  A one-workgroup scan kernel judges every message —
+// keys, ranges (wrap-safe), access rights — writes its ibv_wc_status
+// into d_status[m] and hands the _b engine an effective length of 0 for
+// every message that did not complete with SUCCESS: such a message
+// reaches no load, store or atomic and its digest is 0.  No descriptor
+// is trusted: an offset, address, length or key of any value gives a
+// status, never an access outside an MR.  The table itself is trusted.
+// d_qp_state: null = every message is judged on its own.  Otherwise one
+// device word, 0 = ready: the first message that fails completes with
+// its status, every later one with WR_FLUSH_ERR, and the word is set to
+// 1; a word that is non-zero on entry flushes the whole batch.
+// d_scratch: ROCP2P_PROT_SCRATCH_WORDS(n) 64-bit words.  d_out: n
+// digests or null, max_msg_bytes and grid_cap as for the _b calls.
+// Stream-ordered, allocate nothing, no host synchronise.
+// hipErrorInvalidValue: null d_scratch, d_status or d_mrs, nmr == 0 or
+// nmr > 2^20, base not 16-byte aligned.  n == 0 is a no-op and leaves
+// the word alone.  With a table that covers everything and valid keys
+// the bytes and digests are those of the _b calls.
+hipError_t rocp2p_gather_p(void* dst_base, const uint64_t* d_dst_offs,
+                           const uint64_t* d_src_addrs,
+                           const uint64_t* d_lens, const uint64_t* d_keys,
+                           uint32_t n, const uint64_t* d_mrs, uint32_t nmr,
+                           int32_t* d_qp_state, uint64_t max_msg_bytes,
+                           uint64_t* d_scratch, int32_t* d_status,
+                           uint32_t* d_out, uint32_t grid_cap,
+                           hipStream_t stream);
+hipError_t rocp2p_scatter_p(const void* src_base, const uint64_t* d_src_offs,
+                            const uint64_t* d_dst_addrs,
+                            const uint64_t* d_lens, const uint64_t* d_keys,
+                            uint32_t n, const uint64_t* d_mrs, uint32_t nmr,
+                            int32_t* d_qp_state, uint64_t max_msg_bytes,
+                            uint64_t* d_scratch, int32_t* d_status,
+                            uint32_t* d_out, uint32_t grid_cap,
+                            hipStream_t stream);
+
 }  // extern "C"

@@ -32,6 +32,7 @@
 #include "p2p_varlen.h"
 #include "p2p_bytes.h"
 #include "p2p_sgl.h"
+#include "p2p_prot.h"
 
 #define WAVE 64u
 #define PAGE 4096u
@@ -1666,6 +1667,86 @@ __global__ void __launch_bounds__(WAVE * ICRC_WAVES) k_msg_engine_sg(
 }
 
 // ---------------------------------------------------------------------
+// Memory protection (rules: p2p_prot.h).  k_prot_scan is k_vl_scan_b
+// with a judge in front of it: one workgroup resolves the keys of every
+// message against the MR table, checks both ranges and the access
+// rights, and hands the byte-granular engine effective lengths — a
+// message that is rejected, or flushed behind a rejected one, has the
+// effective length 0, owns no chunk and so reaches no load, store or
+// atomic of k_msg_engine_b, which runs unchanged on elen and cstart.
+// Wave w judges the segment block_scan gives it, so the verdict parked
+// in status[i] is read back by the lane that wrote it.  A table of up to
+// PROT_LDS_MRS entries is staged in LDS (every message reads two of
+// them); a larger one is read where it lies.  With a queue-pair word the
+// first failing message f is the minimum over the whole workgroup: the
+// waves' minima meet in LDS at the one barrier between judging and
+// scanning.  The word is read by every thread before that barrier and
+// written by thread 0 after it.
+#define PROT_LDS_MRS 64u
+template <bool GATHER>
+__global__ void __launch_bounds__(VL_SCAN_THREADS) k_prot_scan(
+    const uint8_t* region, const uint64_t* __restrict__ offs,
+    const uint64_t* __restrict__ addrs, const uint64_t* __restrict__ lens,
+    const uint64_t* __restrict__ keys, uint32_t n,
+    const uint64_t* __restrict__ mrs, uint32_t nmr, int32_t* qp_state,
+    int32_t* status, uint64_t* scratch) {
+  __shared__ uint64_t s_wave[VL_SCAN_THREADS / WAVE];
+  __shared__ uint32_t s_first[VL_SCAN_THREADS / WAVE];
+  __shared__ uint64_t s_mr[PROT_LDS_MRS * ROCP2P_PROT_MR_WORDS];
+  uint64_t* cstart = scratch;
+  uint64_t* elen = scratch + (uint64_t)n + 1;
+  const bool qp = qp_state != nullptr;
+  const bool entry_err = qp && *qp_state != 0;
+  const uint64_t base = reinterpret_cast<uintptr_t>(region);
+  const uint32_t lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+
+  // block_scan's segments
+  const uint64_t per =
+      ((uint64_t)n + VL_SCAN_THREADS - 1) / VL_SCAN_THREADS * WAVE;
+  const uint64_t b = min(wv * per, (uint64_t)n);
+  const uint64_t e = min(b + per, (uint64_t)n);
+  uint32_t first = ROCP2P_PROT_NO_F;
+  auto judge = [&](const uint64_t* tab) {
+    for (uint64_t i = b + lane; i < e; i += WAVE) {
+      const uint32_t v = rocp2p_prot_verdict(tab, nmr, base, offs[i], addrs[i],
+                                             lens[i], keys[i], GATHER);
+      status[i] = (int32_t)v;
+      if (v != ROCP2P_WC_SUCCESS && first == ROCP2P_PROT_NO_F)
+        first = (uint32_t)i;
+    }
+  };
+  if (nmr <= PROT_LDS_MRS) {
+    for (uint32_t i = threadIdx.x; i < nmr * ROCP2P_PROT_MR_WORDS;
+         i += VL_SCAN_THREADS)
+      s_mr[i] = mrs[i];
+    __syncthreads();
+    judge(s_mr);
+  } else {
+    judge(mrs);
+  }
+  for (uint32_t o = WAVE / 2; o; o >>= 1)
+    first = min(first, (uint32_t)__shfl_xor((int)first, o, WAVE));
+  if (lane == 0) s_first[wv] = first;
+  __syncthreads();
+  uint32_t f = ROCP2P_PROT_NO_F;
+  for (uint32_t w = 0; w < VL_SCAN_THREADS / WAVE; w++) f = min(f, s_first[w]);
+  if (qp && threadIdx.x == 0 && (entry_err || f != ROCP2P_PROT_NO_F))
+    *qp_state = 1;
+
+  block_scan<false, true>(
+      [&](uint64_t i) {
+        const uint32_t st = rocp2p_prot_final((uint32_t)status[i], (uint32_t)i,
+                                              f, qp, entry_err);
+        const uint64_t el = rocp2p_prot_elen(st, lens[i]);
+        status[i] = (int32_t)st;
+        elen[i] = el;
+        return rocp2p_b_chunks((uint32_t)(GATHER ? offs[i] : addrs[i]) & 15u,
+                               el);
+      },
+      n, cstart, s_wave);
+}
+
+// ---------------------------------------------------------------------
 // launchers
 
 static inline uint32_t stream_grid(uint64_t items, uint32_t per_block) {
@@ -2201,4 +2282,64 @@ extern "C" hipError_t rocp2p_scatter_sg(
                                      d_sge_start, d_sge_addrs, d_sge_lens, n,
                                      nsge, max_msg_bytes, d_scratch, d_out,
                                      grid_cap, stream);
+}
+
+// ---------------------------------------------------------------------
+// Protected launchers: k_prot_scan, then the unchanged byte-granular
+// engine over the effective lengths, on one stream.  The grid is sized
+// as for rocp2p_gather_b; it depends on no verdict.
+
+template <bool GATHER>
+static hipError_t msg_engine_p_launch(
+    void* region, const uint64_t* d_offs, const uint64_t* d_addrs,
+    const uint64_t* d_lens, const uint64_t* d_keys, uint32_t n,
+    const uint64_t* d_mrs, uint32_t nmr, int32_t* d_qp_state,
+    uint64_t max_msg_bytes, uint64_t* d_scratch, int32_t* d_status,
+    uint32_t* d_out, uint32_t grid_cap, hipStream_t stream) {
+  if (!d_scratch || !d_status || !d_mrs || !nmr ||
+      nmr > ROCP2P_PROT_MAX_MR || (uintptr_t)region % 16)
+    return hipErrorInvalidValue;
+  if (!n) return hipSuccess;
+  hipError_t e = d_out ? crc_out_ready(d_out, n, stream) : hipSuccess;
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_prot_scan<GATHER>, dim3(1), dim3(VL_SCAN_THREADS), 0,
+                     stream, (const uint8_t*)region, d_offs, d_addrs, d_lens,
+                     d_keys, n, d_mrs, nmr, d_qp_state, d_status, d_scratch);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const uint64_t cap =
+      engine_grid_cap(GATHER, d_out != nullptr, max_msg_bytes, grid_cap);
+  const uint32_t grid =
+      vl_grid(n, b_bound(max_msg_bytes), 0, ICRC_WAVES, cap);
+  const uint64_t* d_cstart = d_scratch;
+  const uint64_t* d_elen = d_scratch + (uint64_t)n + 1;
+  return engine_launch(k_msg_engine_b<GATHER, true>,
+                       k_msg_engine_b<GATHER, false>, d_out, grid, stream,
+                       (uint8_t*)region, d_offs, d_addrs, d_elen, d_cstart, n);
+}
+
+extern "C" hipError_t rocp2p_gather_p(
+    void* dst_base, const uint64_t* d_dst_offs, const uint64_t* d_src_addrs,
+    const uint64_t* d_lens, const uint64_t* d_keys, uint32_t n,
+    const uint64_t* d_mrs, uint32_t nmr, int32_t* d_qp_state,
+    uint64_t max_msg_bytes, uint64_t* d_scratch, int32_t* d_status,
+    uint32_t* d_out, uint32_t grid_cap, hipStream_t stream) {
+  return msg_engine_p_launch<true>(dst_base, d_dst_offs, d_src_addrs, d_lens,
+                                   d_keys, n, d_mrs, nmr, d_qp_state,
+                                   max_msg_bytes, d_scratch, d_status, d_out,
+                                   grid_cap, stream);
+}
+
+extern "C" hipError_t rocp2p_scatter_p(
+    const void* src_base, const uint64_t* d_src_offs,
+    const uint64_t* d_dst_addrs, const uint64_t* d_lens,
+    const uint64_t* d_keys, uint32_t n, const uint64_t* d_mrs, uint32_t nmr,
+    int32_t* d_qp_state, uint64_t max_msg_bytes, uint64_t* d_scratch,
+    int32_t* d_status, uint32_t* d_out, uint32_t grid_cap,
+    hipStream_t stream) {
+  // the scatter instantiations only read the region
+  return msg_engine_p_launch<false>(const_cast<void*>(src_base), d_src_offs,
+                                    d_dst_addrs, d_lens, d_keys, n, d_mrs,
+                                    nmr, d_qp_state, max_msg_bytes, d_scratch,
+                                    d_status, d_out, grid_cap, stream);
 }

@@ -45,6 +45,10 @@ def get_transport(name: str, **kw) -> Transport:
 
         return SdmaTransport(**kw)
     if name == "verbs":
+        if kw.get("protected"):
+            raise NotImplementedError(
+                "verbs transport does not implement protected=True (an "
+                "HCA checks its own keys)")
         if kw.get("icrc"):
             raise NotImplementedError(
                 "verbs transport does not implement icrc=True (an HCA "

@@ -53,6 +53,26 @@ read may not overlap: they are written).  `post(i, nbytes)` is
 `post_sg(i, [(0, nbytes)])` there, `post_many_sg(start, n, sges)` posts
 n lists at once and `digest_check_sg(payload, sges)` audits such
 traffic, the slack on the receiving side included.
+
+`protected=True` (opt-in on top of byte_granular=True with max_sge == 1,
+backends that support it) puts memory protection in front of every
+message, as an HCA resolves lkey and rkey before it moves a byte.  The
+transport registers two default MRs at open — the region
+(REMOTE_READ | REMOTE_WRITE, `region_key`) and the staging area
+(LOCAL_WRITE, `staging_key`) —, `reg_mr(side, offset, length, access)`
+registers a window of either side and returns its key, `dereg_mr(key)`
+frees it (the slot's next key carries another tag, so the old key is
+stale).  `post(i, nbytes, rkey=..., lkey=...)` and `post_many` take the
+keys a message is checked with (None = the default keys); the host does
+not check ranges against MRs, the engine does.  Each message completes
+with an `ibv_wc_status` value: `completions()` returns those of the last
+flushed batch in post order, `prot_stats()` the running {"ok", "errors",
+"flushed"} counts.  The transport is one queue pair: the first message
+that fails puts it in the error state, everything posted behind it is
+flushed (WR_FLUSH_ERR, no byte moved) until `reset_qp()`;
+`qp_in_error()` reads the state.  digest_check and integrity_check run
+through the protected engine with the default keys and count a message
+that did not complete with SUCCESS as bad.
 """
 from __future__ import annotations
 
@@ -65,12 +85,17 @@ class Transport(abc.ABC):
     supports_var_len = False
     supports_byte_granular = False
     supports_sg_list = False
+    supports_protection = False
 
     def __init__(self, msg_bytes: int, region_bytes: int,
                  inflight: int | None = 8, direction: str = "write",
                  icrc: bool = False, var_len: bool = False,
                  byte_granular: bool = False, region_skew: int = 0,
-                 staging_skew: int = 0, max_sge: int = 1, **_):
+                 staging_skew: int = 0, max_sge: int = 1,
+                 protected: bool = False, max_mr: int = 16, **_):
+        if protected and not self.supports_protection:
+            raise NotImplementedError(
+                f"{self.name} transport does not implement protected=True")
         if icrc and not self.supports_icrc:
             raise NotImplementedError(
                 f"{self.name} transport does not implement icrc=True")
@@ -105,6 +130,15 @@ class Transport(abc.ABC):
                              "SGE carries its own offset into the slot")
         if max(region_skew, staging_skew) >= msg_bytes:
             raise ValueError("skew leaves no room in a slot of msg_bytes")
+        if protected and not byte_granular:
+            raise ValueError("protected=True needs byte_granular=True: the "
+                             "protected engine is the byte-granular one")
+        if protected and max_sge > 1:
+            raise ValueError("protected=True needs max_sge == 1: keys per "
+                             "SGE are not implemented")
+        if protected and (int(max_mr) != max_mr or
+                          not 2 <= max_mr <= 1 << 20):
+            raise ValueError("max_mr must be an integer in [2, 2^20]")
         if region_bytes % msg_bytes:
             raise ValueError("region must be a multiple of msg size")
         if direction not in ("write", "read"):
@@ -121,6 +155,8 @@ class Transport(abc.ABC):
         self.region_skew = int(region_skew)
         self.staging_skew = int(staging_skew)
         self.max_sge = int(max_sge)
+        self.protected = bool(protected)
+        self.max_mr = int(max_mr)
         # the longest message a slot holds behind the larger skew
         self.max_nbytes = msg_bytes - max(self.region_skew,
                                           self.staging_skew)
@@ -136,11 +172,21 @@ class Transport(abc.ABC):
     def flush(self) -> None:
         """Complete every outstanding message."""
 
-    def post_many(self, start: int, n: int, nbytes=None) -> None:
+    def post_many(self, start: int, n: int, nbytes=None, *, rkey=None,
+                  lkey=None) -> None:
         """Enqueue messages start..start+n-1 (backends may vectorize the
         WQE writes; semantics identical to n post() calls).  nbytes
         (var_len=True only): one byte count for all, or an integer array
-        of n."""
+        of n.  rkey / lkey (protected=True only): one key for all, or an
+        array of n; None = the default keys."""
+        if rkey is not None or lkey is not None:
+            keys = self._keys(rkey, lkey, n)
+            lens = self._lens(nbytes, n)
+            for k in range(n):
+                self.post(start + k, int(lens[k]),
+                          rkey=int(keys[k]) & 0xFFFFFFFF,
+                          lkey=int(keys[k]) >> 32)
+            return
         if nbytes is None:
             for i in range(start, start + n):
                 self.post(i)
@@ -200,6 +246,133 @@ class Transport(abc.ABC):
             raise ValueError(
                 f"nbytes must be a multiple of 16 in [0, {self.msg_bytes}]")
         return ln
+
+    # -- memory protection (protected=True only) -----------------------
+    def _prot_open(self, table, region_base: int, staging_base: int,
+                   staging_bytes: int) -> None:
+        """Start the MR table (a zeroed int64 array [max_mr, 4] the
+        backend owns) with the two default MRs."""
+        from ..utils import prot
+
+        self._mr = table
+        self._mr_tag = [0] * self.max_mr
+        self._mr_dirty = True
+        self._mr_sides = {"region": (region_base, self.region_bytes),
+                          "staging": (staging_base, staging_bytes)}
+        self.region_key = self.reg_mr(
+            "region", 0, self.region_bytes,
+            prot.ACCESS_REMOTE_READ | prot.ACCESS_REMOTE_WRITE)
+        self.staging_key = self.reg_mr("staging", 0, staging_bytes,
+                                       prot.ACCESS_LOCAL_WRITE)
+
+    def _need_protected(self) -> None:
+        if not self.protected:
+            raise ValueError(
+                f"this {self.name} transport was not opened with "
+                "protected=True: it has no MR table and its posts carry "
+                "no keys")
+
+    def reg_mr(self, side: str, offset: int, length: int, access: int) -> int:
+        """Register bytes [offset, offset + length) of the region
+        (side="region") or of the staging area (side="staging") with the
+        verbs access bits `access`; returns the key.  ValueError: a range
+        outside that side, access == 0, a full table."""
+        from ..utils import prot
+
+        self._need_protected()
+        if side not in self._mr_sides:
+            raise ValueError('side must be "region" or "staging"')
+        base, size = self._mr_sides[side]
+        if (int(offset) != offset or int(length) != length or offset < 0
+                or length < 0 or offset + length > size):
+            raise ValueError(f"MR range outside the {side}")
+        if int(access) != access or not 0 < access < 8:
+            raise ValueError("access must be a non-empty set of the "
+                             "LOCAL_WRITE, REMOTE_WRITE, REMOTE_READ bits")
+        free = [r for r in range(self.max_mr) if self._mr[r, 3] == 0]
+        if not free:
+            raise ValueError(f"MR table full (max_mr = {self.max_mr})")
+        slot = free[0]
+        self._mr_tag[slot] = (self._mr_tag[slot] + 1) & 0xFF
+        key = prot.make_key(slot, self._mr_tag[slot])
+        self._mr[slot] = (key, base + int(offset), int(length), int(access))
+        self._mr_dirty = True
+        return key
+
+    def dereg_mr(self, key: int) -> None:
+        """Free the MR `key` names.  ValueError: no such MR."""
+        self._need_protected()
+        slot = int(key) >> 8
+        if not (0 <= slot < self.max_mr and self._mr[slot, 3] != 0
+                and self._mr[slot, 0] == key):
+            raise ValueError(f"unknown MR key {key!r}")
+        self._mr[slot] = 0
+        self._mr_dirty = True
+
+    def _keys(self, rkey, lkey, n: int):
+        """The keys of n posts as an int64 array of lkey << 32 | rkey
+        (None = the default key of that side)."""
+        import numpy as np
+
+        self._need_protected()
+        cols = []
+        for what, k, default in (("lkey", lkey, self.staging_key),
+                                 ("rkey", rkey, self.region_key)):
+            arr = np.asarray(default if k is None else k)
+            if arr.dtype.kind not in "iu":
+                raise ValueError(f"{what} must be integers")
+            if arr.ndim == 0:
+                arr = np.full(n, arr)
+            elif arr.shape != (n,):
+                raise ValueError(f"{what} must be a scalar or {n} entries")
+            arr = arr.astype(np.int64)
+            if ((arr < 0) | (arr >> 32 != 0)).any():
+                raise ValueError(f"{what} must fit 32 bits")
+            cols.append(arr)
+        return (cols[0] << 32) | cols[1]
+
+    def prot_expected(self, start: int, n: int, nbytes=None, *, rkey=None,
+                      lkey=None, qp_state=0):
+        """What the rules give for post_many(start, n, nbytes, rkey=...,
+        lkey=...) against the MR table as it stands and a queue pair in
+        state qp_state: (status, elens, qp_state_out) of
+        utils.prot.prot_reference.  The model, not the engine."""
+        import numpy as np
+
+        from ..utils import prot
+
+        keys = self._keys(rkey, lkey, n)
+        lens = self._lens(nbytes, n)
+        idx = np.arange(start, start + n, dtype=np.int64)
+        offs = (idx % self.msgs_per_region) * self.msg_bytes + \
+            self.region_skew
+        addrs = (self._mr_sides["staging"][0] + self.staging_skew
+                 + (idx % self.inflight) * self.msg_bytes)
+        return prot.prot_reference(
+            np.array(self._mr), self._mr_sides["region"][0], offs, addrs,
+            lens, keys, self.direction == "write", qp_state=qp_state)
+
+    def completions(self):
+        """The ibv_wc_status of every message of the last flushed batch,
+        in post order (int32 numpy array)."""
+        self._need_protected()
+        raise NotImplementedError
+
+    def prot_stats(self) -> dict:
+        """{"ok": messages completed with SUCCESS so far, "errors": with
+        an error status of their own, "flushed": with WR_FLUSH_ERR}."""
+        self._need_protected()
+        raise NotImplementedError
+
+    def qp_in_error(self) -> bool:
+        """Has a message failed since open / the last reset_qp()?"""
+        self._need_protected()
+        raise NotImplementedError
+
+    def reset_qp(self) -> None:
+        """Leave the error state: messages posted from here on move."""
+        self._need_protected()
+        raise NotImplementedError
 
     # -- scatter/gather lists (max_sge > 1 only) -----------------------
     def post_sg(self, i: int, sges) -> None:

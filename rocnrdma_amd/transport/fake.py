@@ -17,6 +17,7 @@ class FakeTransport(Transport):
     supports_var_len = True
     supports_byte_granular = True
     supports_sg_list = True  # numpy and zlib: the sdma logic, CPU tier
+    supports_protection = True  # utils.prot: the sdma logic, CPU tier
     KNOWN = 0x5A  # what digest_check(payload, lens) leaves in the slack
 
     def __init__(self, msg_bytes: int, region_bytes: int, **kw):
@@ -27,13 +28,29 @@ class FakeTransport(Transport):
             self._expected = None  # per slot (write) / per message (read)
             self._checked = self._bad = 0
             self._inline = None  # digests of a running digest_check
+        if self.protected:
+            # the "addresses" the MRs and the posts speak of are those of
+            # the two numpy buffers; one ring of `inflight` posts per batch
+            self._prot_open(np.zeros((self.max_mr, 4), dtype=np.int64),
+                            self.region.ctypes.data,
+                            self.staging.ctypes.data,
+                            self.inflight * msg_bytes)
+            self._qp = 0
+            self._batch = []  # statuses of the posts since the last flush
+            self._last = np.zeros(0, dtype=np.int32)
+            self._stats = {"ok": 0, "errors": 0, "flushed": 0}
+            self._sink = None  # statuses of a running check, post order
 
-    def post(self, i: int, nbytes: int | None = None) -> None:
+    def post(self, i: int, nbytes: int | None = None, *, rkey=None,
+             lkey=None) -> None:
         ln = self._len1(nbytes)
         ss = self.staging_skew
         slot = self.staging[i % self.inflight][ss : ss + ln]
         off = (i % self.msgs_per_region) * self.msg_bytes + self.region_skew
         dst = self.region[off : off + ln]
+        if self.protected or rkey is not None or lkey is not None:
+            if not self._judge(i, off, ln, self._keys(rkey, lkey, 1)):
+                return
         if self.icrc:
             self._digest(i, slot if self.direction == "write" else dst)
         if self.direction == "write":
@@ -72,8 +89,73 @@ class FakeTransport(Transport):
             self._checked += 1
             self._bad += int(crc != int(self._expected[k]))
 
+    def _judge(self, i: int, off: int, ln: int, keys) -> bool:
+        """The protected engine's verdict on one post, taken when it is
+        posted (this backend moves data in post()); False = nothing
+        moves.  The ring is flushed when it is full, as sdma's is."""
+        from ..utils import prot
+
+        if len(self._batch) >= self.inflight:
+            self.flush()
+        addr = (self.staging.ctypes.data
+                + (i % self.inflight) * self.msg_bytes + self.staging_skew)
+        st, _, self._qp = prot.prot_reference(
+            self._mr, self.region.ctypes.data, [off], [addr], [ln], keys,
+            self.direction == "write", qp_state=self._qp)
+        self._batch.append(int(st[0]))
+        if st[0] != prot.WC_SUCCESS and self.icrc \
+                and self._inline is not None:
+            self._inline.append(0)  # what the engine leaves for it
+        return st[0] == prot.WC_SUCCESS
+
     def flush(self) -> None:  # synchronous backend
-        pass
+        if self.protected and self._batch:
+            from ..utils import prot
+
+            st = np.array(self._batch, dtype=np.int32)
+            self._batch = []
+            self._last = st
+            self._stats["ok"] += int((st == prot.WC_SUCCESS).sum())
+            self._stats["flushed"] += int((st == prot.WC_WR_FLUSH_ERR).sum())
+            self._stats["errors"] += int(
+                ((st != prot.WC_SUCCESS) & (st != prot.WC_WR_FLUSH_ERR)).sum())
+            if self._sink is not None:
+                self._sink.append(st)
+
+    def completions(self):
+        self._need_protected()
+        return self._last.copy()
+
+    def prot_stats(self) -> dict:
+        self._need_protected()
+        self.flush()
+        return dict(self._stats)
+
+    def qp_in_error(self) -> bool:
+        self._need_protected()
+        return self._qp != 0
+
+    def reset_qp(self) -> None:
+        self._need_protected()
+        self.flush()
+        self._qp = 0
+
+    def _rejected(self, run):
+        """run() a check's posts and flushes; the boolean array of its
+        messages, in post order, that did not complete with SUCCESS
+        (nothing is rejected without protected=True)."""
+        if not self.protected:
+            return run(), False
+        self.flush()
+        self._sink = []
+        try:
+            res = run()
+            self.flush()
+            st = (np.concatenate(self._sink) if self._sink
+                  else np.zeros(0, dtype=np.int32))
+        finally:
+            self._sink = None
+        return res, st != 0
 
     def stamp(self) -> None:
         if not self.icrc or self.var_len:
@@ -91,6 +173,10 @@ class FakeTransport(Transport):
         return {"checked": self._checked, "bad": self._bad}
 
     def integrity_check(self, seed: int) -> int:
+        bad, rejected = self._rejected(lambda: self._integrity_check(seed))
+        return bad + int(np.sum(rejected))
+
+    def _integrity_check(self, seed: int) -> int:
         self._no_pattern_with_skew()
         if self.icrc:
             self._expected = None  # the sender is rewritten below
@@ -122,7 +208,10 @@ class FakeTransport(Transport):
         pay = self._payload_bytes(payload)
         n, msg = self.msgs_per_region, self.msg_bytes
         if self.var_len or lens is not None:
-            return self._digest_check_var(pay, self._lens(lens, n))
+            lens = self._lens(lens, n)
+            bad, rejected = self._rejected(
+                lambda: self._digest_check_var(pay, lens))
+            return int((bad | rejected).sum())
         if self.icrc:
             # the region-side digests come from the inline ICRC of the
             # transfer itself, not from a second pass over the region
@@ -161,7 +250,8 @@ class FakeTransport(Transport):
     def _digest_check_var(self, pay, lens) -> int:
         """digest_check for per-message lengths: digests of the lens[j]
         bytes at the skew (0 unless byte_granular), and the receiver's
-        slack — the slot outside the message — must keep KNOWN."""
+        slack — the slot outside the message — must keep KNOWN.  Returns
+        the boolean array of bad messages."""
         n, msg = self.msgs_per_region, self.msg_bytes
         ss, rs = self.staging_skew, self.region_skew
         write = self.direction == "write"
@@ -191,7 +281,7 @@ class FakeTransport(Transport):
                     slot = self.region[i * msg : (i + 1) * msg]
                     bad[i] |= bool((slot[:rs] != self.KNOWN).any() or
                                    (slot[rs + lens[i]:] != self.KNOWN).any())
-                return int(bad.sum())
+                return bad
             # read: load the region, pull every message into a slot that
             # holds KNOWN, digest and inspect the slot
             self.region[:] = pay
@@ -211,7 +301,7 @@ class FakeTransport(Transport):
                 bad[i] = (got != want or
                           bool((slot[:ss] != self.KNOWN).any()) or
                           bool((slot[ss + ln:] != self.KNOWN).any()))
-            return int(bad.sum())
+            return bad
         finally:
             if self.icrc:
                 self._inline = None

@@ -41,6 +41,13 @@ a hardware WQE has: a list with fewer SGEs leaves the others at length
 0, so the CSR row starts are the constant arange(inflight + 1) * K, built
 once on the device.  flush() retires the ring with one
 ops.gather_sg_/scatter_sg_ launch (crc=icrc) on the flush stream.
+
+protected=True (on top of byte_granular, max_sge == 1) gives every WQE a
+key word (lkey << 32 | rkey) and retires the ring with
+ops.gather_prot_/scatter_prot_ (crc=icrc): the MR table lives in pinned
+memory and is copied to the device at the next flush after it changed,
+the queue-pair state word and the {"ok", "errors", "flushed"} counters
+live on the device and are updated on the flush stream.
 """
 from __future__ import annotations
 
@@ -53,9 +60,10 @@ _KERNEL_THRESHOLD = 8 << 20
 _STAGING_TARGET = 64 << 20  # pinned staging budget for small messages
 
 # Rows of the WQE ring.  The optional rows follow in this order: the
-# message's byte count (var_len), then what the inline digest is compared
-# with (icrc): the expected CRC32 of the slot (write), or the region
-# message whose stamp stays on the device (read).
+# message's byte count (var_len), then its keys (protected), then what
+# the inline digest is compared with (icrc): the expected CRC32 of the
+# slot (write), or the region message whose stamp stays on the device
+# (read).
 ROW_OFF, ROW_ADDR = 0, 1  # region offset, staging address
 _KNOWN = 0x5A  # what digest_check(payload, lens) leaves in the slack
 
@@ -66,6 +74,7 @@ class SdmaTransport(Transport):
     supports_var_len = True
     supports_byte_granular = True
     supports_sg_list = True
+    supports_protection = True
 
     def __init__(self, msg_bytes: int, region_bytes: int, device=None,
                  num_streams: int = 2, engine: str = "auto",
@@ -92,6 +101,12 @@ class SdmaTransport(Transport):
                 "a scatter/gather list; the stream engine (explicit, or "
                 "picked by auto for slots of 8 MiB and up) copies whole "
                 "slots")
+        if kw.get("protected") and engine != "kernel":
+            raise ValueError(
+                "protected=True needs the kernel engine: only its WQEs "
+                "carry keys and only a kernel can judge them; the stream "
+                "engine (explicit, or picked by auto for slots of 8 MiB "
+                "and up) copies whole slots")
         if inflight in (None, 0):
             if engine == "kernel":
                 inflight = max(8, min(region_bytes // msg_bytes,
@@ -121,9 +136,11 @@ class SdmaTransport(Transport):
             self._slot_addr_np = np.array(self._slot_addr, dtype=np.int64)
             # WQE ring: ROW_OFF, ROW_ADDR, then the optional rows
             rows = 2
-            self._row_len = self._row_exp = None
+            self._row_len = self._row_exp = self._row_key = None
             if self.var_len:
                 self._row_len, rows = rows, rows + 1
+            if self.protected:
+                self._row_key, rows = rows, rows + 1
             if self.icrc:
                 self._row_exp, rows = rows, rows + 1
             self._desc_pin = torch.empty((rows, self.inflight),
@@ -146,6 +163,23 @@ class SdmaTransport(Transport):
                     self.inflight + 1, dtype=torch.int64,
                     device=self.device) * K
                 torch.cuda.synchronize(self.device)
+        if self.protected:
+            self._mr_pin = torch.zeros((self.max_mr, 4), dtype=torch.int64,
+                                       pin_memory=True)
+            self._mr_dev = torch.zeros((self.max_mr, 4), dtype=torch.int64,
+                                       device=self.device)
+            self._prot_open(self._mr_pin.numpy(), self.region.data_ptr(),
+                            self.staging_flat.data_ptr(),
+                            self.inflight * msg_bytes)
+            self._qp_dev = torch.zeros(1, dtype=torch.int32,
+                                       device=self.device)
+            # ok, errors, flushed
+            self._prot_dev = torch.zeros(3, dtype=torch.int64,
+                                         device=self.device)
+            self._last_status = None  # of the last flushed batch
+            self._sink = None  # statuses of a running check, post order
+            self._last_digests = None
+            torch.cuda.synchronize(self.device)
         if self.icrc:
             self._stamped = False
             self._exp_slot_np = None  # write: int32-wrapped CRC per slot
@@ -158,7 +192,11 @@ class SdmaTransport(Transport):
             torch.cuda.synchronize(self.device)
 
     # -- data plane ----------------------------------------------------
-    def post(self, i: int, nbytes: int | None = None) -> None:
+    def post(self, i: int, nbytes: int | None = None, *, rkey=None,
+             lkey=None) -> None:
+        keys = None
+        if self.protected or rkey is not None or lkey is not None:
+            keys = self._keys(rkey, lkey, 1)
         if self.max_sge > 1:
             return self.post_sg(i, [(0, self._len1(nbytes))])
         if nbytes is not None or self.var_len:
@@ -173,6 +211,8 @@ class SdmaTransport(Transport):
             self._desc_np[ROW_ADDR, k] = self._slot_addr[slot]
             if self.var_len:
                 self._desc_np[self._row_len, k] = nbytes
+            if keys is not None:
+                self._desc_np[self._row_key, k] = keys[0]
             if self.icrc and self._stamped:
                 self._desc_np[self._row_exp, k] = (
                     self._exp_slot_np[slot] if self.direction == "write"
@@ -187,13 +227,18 @@ class SdmaTransport(Transport):
             else:
                 self.staging[slot].copy_(dst, non_blocking=True)
 
-    def post_many(self, start: int, n: int, nbytes=None) -> None:
+    def post_many(self, start: int, n: int, nbytes=None, *, rkey=None,
+                  lkey=None) -> None:
         """Vectorized WQE writes (numpy) — the posting loop itself must
         not bound small-message rates (a verbs app posts in C; measured:
         scalar python post() capped 4 KiB at ~10 GB/s)."""
         if self.engine != "kernel":
-            return super().post_many(start, n, nbytes)
+            return super().post_many(start, n, nbytes, rkey=rkey, lkey=lkey)
         import numpy as np
+
+        keys = None
+        if self.protected or rkey is not None or lkey is not None:
+            keys = self._keys(rkey, lkey, n)
 
         if self.max_sge > 1:  # one SGE each: the slot's first nbytes
             sges = np.zeros((n, self.max_sge, 2), dtype=np.int64)
@@ -218,6 +263,9 @@ class SdmaTransport(Transport):
             if lens is not None:
                 self._desc_np[self._row_len, k:k + take] = \
                     lens[done:done + take]
+            if keys is not None:
+                self._desc_np[self._row_key, k:k + take] = \
+                    keys[done:done + take]
             if self.icrc and self._stamped:
                 self._desc_np[self._row_exp, k:k + take] = (
                     self._exp_slot_np[idx % self.inflight]
@@ -267,6 +315,8 @@ class SdmaTransport(Transport):
                                                 non_blocking=True)
                     if self.max_sge > 1:
                         self._flush_sg(n)
+                    elif self.protected:
+                        self._flush_prot(n)
                     elif self.var_len:
                         self._flush_var_len(n)
                     elif self.icrc:
@@ -318,6 +368,77 @@ class SdmaTransport(Transport):
         if self.icrc:
             self._last_digests = dig
 
+    def _flush_prot(self, n: int) -> None:
+        """One protected engine launch for the ring, on the current
+        (flush) stream: the MR table first if it changed, then the
+        launch against the transport's queue-pair word; the statuses of
+        the batch are kept and counted on the same stream."""
+        from .. import ops
+
+        if self._mr_dirty:
+            self._mr_dev.copy_(self._mr_pin, non_blocking=True)
+            self._mr_dirty = False
+        engine = (ops.gather_prot_ if self.direction == "write"
+                  else ops.scatter_prot_)
+        st, dig = engine(self.region, self._desc_dev[ROW_OFF, :n],
+                         self._desc_dev[ROW_ADDR, :n],
+                         self._desc_dev[self._row_len, :n],
+                         self._desc_dev[self._row_key, :n], self._mr_dev,
+                         qp_state=self._qp_dev, max_msg_bytes=self.msg_bytes,
+                         crc=self.icrc)
+        self._last_status = st
+        if self.icrc:
+            self._last_digests = dig
+        ok = (st == ops.WC_SUCCESS).sum()
+        flushed = (st == ops.WC_WR_FLUSH_ERR).sum()
+        self._prot_dev[0].add_(ok)
+        self._prot_dev[1].add_(n - ok - flushed)
+        self._prot_dev[2].add_(flushed)
+        if self._sink is not None:
+            self._sink.append(st)
+
+    def completions(self):
+        import numpy as np
+
+        self._need_protected()
+        if self._last_status is None:
+            return np.zeros(0, dtype=np.int32)
+        return self._last_status.cpu().numpy()
+
+    def prot_stats(self) -> dict:
+        self._need_protected()
+        self.flush()
+        ok, errors, flushed = self._prot_dev.tolist()
+        return {"ok": ok, "errors": errors, "flushed": flushed}
+
+    def qp_in_error(self) -> bool:
+        self._need_protected()
+        self.flush()
+        return bool(self._qp_dev.item())
+
+    def reset_qp(self) -> None:
+        self._need_protected()
+        self.flush()
+        with torch.cuda.stream(self.streams[0]):
+            self._qp_dev.zero_()
+        self.streams[0].synchronize()
+
+    def _rejected(self, run):
+        """run() a check's posts and flushes; the boolean array of its
+        messages, in post order, that did not complete with SUCCESS
+        (nothing is rejected without protected=True)."""
+        if not self.protected:
+            return run(), False
+        self.flush()
+        self._sink = []
+        try:
+            res = run()
+            self.flush()
+            st = torch.cat(self._sink).cpu().numpy()
+        finally:
+            self._sink = None
+        return res, st != 0
+
     def _flush_sg(self, n: int) -> None:
         """One scatter/gather engine launch for the ring, on the current
         (flush) stream; with icrc the digests of the batch are kept."""
@@ -367,6 +488,10 @@ class SdmaTransport(Transport):
 
     # -- integrity plane ----------------------------------------------
     def integrity_check(self, seed: int) -> int:
+        bad, rejected = self._rejected(lambda: self._integrity_check(seed))
+        return bad + int(rejected.sum() if self.protected else 0)
+
+    def _integrity_check(self, seed: int) -> int:
         from .. import ops
 
         self._no_pattern_with_skew()
@@ -419,7 +544,10 @@ class SdmaTransport(Transport):
         pay_t = torch.from_numpy(pay)
         n, msg = self.msgs_per_region, self.msg_bytes
         if self.var_len or lens is not None:
-            return self._digest_check_var_len(pay_t, self._lens(lens, n))
+            lens = self._lens(lens, n)
+            bad, rejected = self._rejected(
+                lambda: self._digest_check_var_len(pay_t, lens))
+            return int((bad | rejected).sum())
         if self.icrc:
             return self._digest_check_icrc(pay_t)
         if self.direction == "write":
@@ -498,7 +626,8 @@ class SdmaTransport(Transport):
         the slack ranges against the digest of that many _KNOWN bytes,
         on the host numpy.  With byte_granular the messages sit at the
         skews, the launches are crc32_messages_bytes and the slack is
-        the slot in front of and behind the message."""
+        the slot in front of and behind the message.  Returns the
+        boolean array of bad messages."""
         import zlib
 
         import numpy as np
@@ -572,7 +701,7 @@ class SdmaTransport(Transport):
                 bad |= (front.cpu().numpy().view(np.uint32)
                         != zlib.crc32(bytes([_KNOWN]) * rs))
         bad |= hbm.cpu().numpy().view(np.uint32) != host
-        return int(bad.sum())
+        return bad
 
     def digest_check_sg(self, payload, sges) -> int:
         """digest_check for scatter/gather traffic (see the base class).
