@@ -251,24 +251,7 @@ def _prot_cycle(tp, rng: random.Random, region: int, stats: dict):
     msg, mpr, inflight = tp.msg_bytes, tp.msgs_per_region, tp.inflight
     rs, ss = tp.region_skew, tp.staging_skew
     write = tp.direction == "write"
-    on_gpu = hasattr(tp, "staging_flat")
-    if on_gpu:
-        import torch
-
-        staging = tp.staging_flat.numpy().reshape(inflight, msg)
-    else:
-        staging = tp.staging
-
-    def region_get():
-        return tp.region.cpu().numpy() if on_gpu else tp.region
-
-    def region_set(arr):
-        if on_gpu:
-            tp.region.copy_(torch.from_numpy(arr))
-            torch.cuda.synchronize(tp.device)
-        else:
-            tp.region[:] = arr
-
+    staging = tp._slots
     g = np.random.default_rng(rng.getrandbits(32))
     # the window: a run of whole region messages, every right granted
     w0 = rng.randrange(mpr)
@@ -300,7 +283,7 @@ def _prot_cycle(tp, rng: random.Random, region: int, stats: dict):
             staging[slots] = _PROT_KNOWN
             for k in range(burst):
                 reg[rmsg[k] * msg:(rmsg[k] + 1) * msg] = data[k]
-        region_set(reg)
+        tp._region_set(reg)
         want, elens, _ = tp.prot_expected(posted, burst, lens, rkey=rkeys)
         tp.post_many(posted, burst, lens, rkey=rkeys)
         tp.flush()
@@ -310,7 +293,7 @@ def _prot_cycle(tp, rng: random.Random, region: int, stats: dict):
             mism[:] = True
         else:
             mism |= got != want
-        reg = region_get()
+        reg = tp._region_get()
         for k in range(burst):
             ln = int(elens[k])
             there = reg[rmsg[k] * msg:(rmsg[k] + 1) * msg]

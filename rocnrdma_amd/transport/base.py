@@ -78,6 +78,20 @@ from __future__ import annotations
 
 import abc
 
+KNOWN = 0x5A  # what digest_check(payload, lens) leaves in the slack
+
+
+def _known_crc32(lens):
+    """zlib's CRC32 of lens[m] KNOWN bytes for every m (uint32 numpy),
+    computed once per distinct length."""
+    import zlib
+
+    import numpy as np
+
+    crc = {int(k): zlib.crc32(bytes([KNOWN]) * int(k))
+           for k in np.unique(lens)}
+    return np.array([crc[int(k)] for k in lens], dtype=np.uint32)
+
 
 class Transport(abc.ABC):
     name = "base"
@@ -458,14 +472,98 @@ class Transport(abc.ABC):
         afterwards the SGE ranges must carry the pieces in order and
         every other slot byte must still be known.  Returns the number
         of bad messages."""
-        raise NotImplementedError(
-            f"{self.name} transport does not implement digest_check_sg")
+        pay = self._payload_bytes(payload)
+        n = self.msgs_per_region
+        sges = self._sges(sges, n)
+        return int(self._audit(
+            pay, sges, True,
+            lambda i, b: self.post_many_sg(i, b, sges[i:i + b])).sum())
 
     # -- integrity plane (never timed) ---------------------------------
-    @abc.abstractmethod
+    # What a backend supplies to the checks below; one that supplies
+    # none has post() and flush() only and overrides integrity_check.
+    #   _slots                  the staging area as one host numpy view
+    #                           (inflight, msg_bytes)
+    #   _region_set(arr)        load the region from a host uint8 array
+    #   _region_fill(byte)      set every region byte
+    #   _region_get()           the region as a host uint8 array
+    #   _region_digests(offs, lens, bound)
+    #                           CRC32 of region[offs[m] : offs[m] + lens[m]]
+    #                           for every m as uint32 numpy; lens <= bound
+    #   _region_pattern(seed)   load the region with the fill pattern
+    #   _region_mismatches(seed)
+    #                           8-byte region words that differ from it
+    #   _gather_host(batches)   the per-batch arrays flush() left (statuses
+    #                           in _sink, digests in _last_digests), joined
+    #                           into one host numpy array
+    # and two attributes its flush() keeps: _last_digests (icrc: the
+    # inline digests of the batch just flushed) and _sink (protected: when
+    # it is a list, the statuses of every flushed batch are appended).
+    def _no_checks(self, *_):
+        raise NotImplementedError(
+            f"{self.name} transport does not implement digest_check")
+
+    _slots = property(_no_checks)
+    _region_set = _region_fill = _region_get = _region_digests = _no_checks
+    _region_pattern = _region_mismatches = _gather_host = _no_checks
+
+    def _bursts(self):
+        """(first message, count) of every burst of a walk over the
+        region: the slots are reused, so a burst must complete before the
+        next one loads them."""
+        n = self.msgs_per_region
+        for i in range(0, n, self.inflight):
+            yield i, min(self.inflight, n - i)
+
+    def _rejected(self, run):
+        """run() a check's posts and flushes; the boolean array of its
+        messages, in post order, that did not complete with SUCCESS
+        (nothing is rejected without protected=True)."""
+        if not self.protected:
+            return run(), False
+        self.flush()
+        self._sink = []
+        try:
+            res = run()
+            self.flush()
+            st = self._gather_host(self._sink)
+        finally:
+            self._sink = None
+        return res, st != 0
+
     def integrity_check(self, seed: int) -> int:
         """Move the whole region with pattern payloads; return mismatching
         8-byte words at the receiver (0 = intact)."""
+        import numpy as np
+
+        from ..utils import pattern
+
+        self._no_pattern_with_skew()
+        if self.icrc:
+            self._stamped = False  # the sender is rewritten below
+        msg, slots = self.msg_bytes, self._slots
+        ref = pattern.fill_reference(self.region_bytes, seed).reshape(-1, msg)
+        write = self.direction == "write"
+
+        def run():
+            if not write:
+                self._region_pattern(seed)
+            bad = 0
+            for i, burst in self._bursts():
+                for j in range(i, i + burst):
+                    if write:
+                        slots[j % self.inflight] = ref[j]
+                    self.post(j)
+                self.flush()
+                if not write:
+                    for j in range(i, i + burst):
+                        bad += int(np.count_nonzero(
+                            slots[j % self.inflight].view(np.uint64)
+                            != ref[j].view(np.uint64)))
+            return self._region_mismatches(seed) if write else bad
+
+        bad, rejected = self._rejected(run)
+        return bad + int(np.sum(rejected))
 
     def digest_check(self, payload, lens=None) -> int:
         """Payload-agnostic check: move the whole region carrying
@@ -482,8 +580,108 @@ class Transport(abc.ABC):
         slack changed.  With byte_granular the sender holds those bytes
         at its skew and the slack is the whole slot outside
         [skew, skew + lens[j]), in front of and behind the message."""
-        raise NotImplementedError(
-            f"{self.name} transport does not implement digest_check")
+        import numpy as np
+
+        pay = self._payload_bytes(payload)
+        n = self.msgs_per_region
+        if self.var_len or lens is not None:
+            lens = self._lens(lens, n)
+            at = self.staging_skew
+
+            def post(i, b):
+                self.post_many(i, b, lens[i:i + b])
+        else:  # whole slots: nothing of the receiver is slack
+            lens, at, post = np.full(n, self.msg_bytes), 0, self.post_many
+        pieces = np.stack([np.full(n, at), lens], axis=1)[:, None, :]
+        return int(self._audit(pay, pieces, self.var_len, post).sum())
+
+    def _audit(self, pay, pieces, slack: bool, post):
+        """The one statement of digest_check and digest_check_sg.  Message
+        j is the concatenation of the staging-slot ranges pieces[j] — an
+        (n, K, 2) array of (slot_off, nbytes) — and sits in the region at
+        j * msg_bytes + region_skew; post(i, b) posts messages i..i+b-1.
+        Per burst: load and digest the sender slots (write) or set the
+        slots to KNOWN (read, slack), post, flush() once, keep the inline
+        digests (icrc), digest and inspect the received slots (read).  The
+        far side is digested by the engine while it moves (icrc) or by
+        _region_digests afterwards, so only 4 bytes per message come back
+        from it.  With slack the receiver starts as KNOWN everywhere and
+        every byte outside the message must still hold it: in a slot a
+        compare, in the region the digest of the range against the CRC32
+        of that many KNOWN bytes.  Returns the boolean array of bad
+        messages: a digest differs, the slack changed, or (protected) the
+        message did not complete with SUCCESS."""
+        import zlib
+
+        import numpy as np
+
+        n, msg, ring = self.msgs_per_region, self.msg_bytes, self.inflight
+        ss, rs = self.staging_skew, self.region_skew
+        write = self.direction == "write"
+        slots = self._slots
+        lens = pieces[:, :, 1].sum(axis=1)
+        offs = np.arange(n, dtype=np.int64) * msg + rs
+        if self.icrc:
+            self._stamped = False  # the sender is rewritten below
+        if not write:  # the first L_j payload bytes of the slot, at the skew
+            reg = pay.copy() if rs else pay
+            for j in range(n if rs else 0):
+                reg[offs[j]:offs[j] + lens[j]] = \
+                    pay[j * msg:j * msg + lens[j]]
+            self._region_set(reg)
+        elif slack:
+            self._region_fill(KNOWN)
+
+        def digest(j):  # zlib over the concatenated pieces of the slot
+            crc = 0
+            for o, k in pieces[j]:
+                crc = zlib.crc32(slots[j % ring][o:o + k], crc)
+            return crc
+
+        host = np.empty(n, dtype=np.uint32)
+        bad = np.zeros(n, dtype=bool)
+        inline = []
+
+        def run():
+            for i, burst in self._bursts():
+                if write:
+                    for j in range(i, i + burst):
+                        slot = slots[j % ring]
+                        slot[:] = pay[j * msg:(j + 1) * msg]
+                        if ss:
+                            slot[ss:ss + lens[j]] = \
+                                pay[j * msg:j * msg + lens[j]]
+                        host[j] = digest(j)
+                elif slack:
+                    slots[:burst] = KNOWN
+                post(i, burst)
+                self.flush()
+                if self.icrc:
+                    inline.append(self._last_digests)
+                if not write:
+                    for j in range(i, i + burst):
+                        host[j] = digest(j)
+                        if slack:
+                            rest = np.ones(msg, dtype=bool)
+                            for o, k in pieces[j]:
+                                rest[o:o + k] = False
+                            bad[j] = (slots[j % ring][rest] != KNOWN).any()
+
+        _, rejected = self._rejected(run)
+        if self.icrc:
+            far = self._gather_host(inline).view(np.uint32)
+        else:
+            far = self._region_digests(offs, lens, msg)
+        bad |= far != host
+        if write and slack:
+            behind = msg - rs - lens
+            front = np.full(n, rs, dtype=np.int64)
+            bad |= (self._region_digests(offs + lens, behind, msg)
+                    != _known_crc32(behind))
+            if rs:
+                bad |= (self._region_digests(offs - rs, front, 16)
+                        != _known_crc32(front))
+        return bad | rejected
 
     # -- inline ICRC (icrc=True only) ----------------------------------
     def stamp(self) -> None:

@@ -53,7 +53,6 @@ from __future__ import annotations
 
 import torch
 
-from ..utils import pattern
 from .base import Transport
 
 _KERNEL_THRESHOLD = 8 << 20
@@ -65,7 +64,6 @@ _STAGING_TARGET = 64 << 20  # pinned staging budget for small messages
 # slot (write), or the region message whose stamp stays on the device
 # (read).
 ROW_OFF, ROW_ADDR = 0, 1  # region offset, staging address
-_KNOWN = 0x5A  # what digest_check(payload, lens) leaves in the slack
 
 
 class SdmaTransport(Transport):
@@ -423,22 +421,6 @@ class SdmaTransport(Transport):
             self._qp_dev.zero_()
         self.streams[0].synchronize()
 
-    def _rejected(self, run):
-        """run() a check's posts and flushes; the boolean array of its
-        messages, in post order, that did not complete with SUCCESS
-        (nothing is rejected without protected=True)."""
-        if not self.protected:
-            return run(), False
-        self.flush()
-        self._sink = []
-        try:
-            res = run()
-            self.flush()
-            st = torch.cat(self._sink).cpu().numpy()
-        finally:
-            self._sink = None
-        return res, st != 0
-
     def _flush_sg(self, n: int) -> None:
         """One scatter/gather engine launch for the ring, on the current
         (flush) stream; with icrc the digests of the batch are kept."""
@@ -486,307 +468,56 @@ class SdmaTransport(Transport):
         checked, bad = self._icrc_dev.tolist()
         return {"checked": checked, "bad": bad}
 
-    # -- integrity plane ----------------------------------------------
-    def integrity_check(self, seed: int) -> int:
-        bad, rejected = self._rejected(lambda: self._integrity_check(seed))
-        return bad + int(rejected.sum() if self.protected else 0)
+    # -- integrity plane: what the checks of the base class work on -----
+    @property
+    def _slots(self):
+        return self.staging_flat.numpy().reshape(self.inflight,
+                                                 self.msg_bytes)
 
-    def _integrity_check(self, seed: int) -> int:
+    def _region_set(self, arr) -> None:
+        self.region.copy_(torch.from_numpy(arr))
+        torch.cuda.synchronize(self.device)
+
+    def _region_fill(self, byte: int) -> None:
+        self.region.fill_(byte)
+        torch.cuda.synchronize(self.device)
+
+    def _region_get(self):
+        return self.region.cpu().numpy()
+
+    def _region_digests(self, offs, lens, bound: int):
+        """One launch over the region, so only 4 bytes per message ever
+        cross back — no payload readback: crc32_messages for the whole
+        slots of a transport without var_len, crc32_messages_v with it,
+        crc32_messages_bytes with byte_granular."""
+        import numpy as np
+
         from .. import ops
 
-        self._no_pattern_with_skew()
-        if self.icrc:
-            self._stamped = False  # the sender is rewritten below
-        ref = pattern.fill_reference(self.region_bytes, seed)
-        ref_t = torch.from_numpy(ref.copy())
-        if self.direction == "write":
-            i = 0
-            while i < self.msgs_per_region:
-                burst = min(self.inflight, self.msgs_per_region - i)
-                for j in range(i, i + burst):
-                    off = j * self.msg_bytes
-                    self.staging[j % self.inflight].copy_(
-                        ref_t[off:off + self.msg_bytes])
-                    self.post(j)
-                self.flush()  # slots reused next burst: must complete
-                i += burst
-            # on-GPU verification — no host readback
-            return int(ops.verify(self.region, seed))
-        # read: pattern HBM with the fill kernel, pull to host, check there
+        if not self.var_len:
+            got = ops.crc32_messages(self.region, self.msg_bytes)
+        else:
+            crc_v = (ops.crc32_messages_bytes if self.byte_granular
+                     else ops.crc32_messages_v)
+            got = crc_v(self.region, torch.from_numpy(offs).to(self.device),
+                        torch.from_numpy(lens).to(self.device),
+                        max_msg_bytes=bound)
+        return got.cpu().numpy().view(np.uint32)
+
+    def _region_pattern(self, seed: int) -> None:
+        from .. import ops
+
         ops.fill_(self.region, seed)
         torch.cuda.synchronize(self.device)
-        bad = 0
-        i = 0
-        while i < self.msgs_per_region:
-            burst = min(self.inflight, self.msgs_per_region - i)
-            for j in range(i, i + burst):
-                self.post(j)
-            self.flush()
-            for j in range(i, i + burst):
-                off = j * self.msg_bytes
-                got = self.staging[j % self.inflight].numpy()
-                want = ref[off:off + self.msg_bytes]
-                bad += int((got.view("u8") != want.view("u8")).sum())
-            i += burst
-        return bad
 
-    def digest_check(self, payload, lens=None) -> int:
-        """Per-message CRC32 of arbitrary content, sender vs receiver.
-        The HBM side is digested by one crc32_messages launch, so only
-        4 bytes per message ever cross back — no payload readback."""
-        import zlib
-
-        import numpy as np
-
+    def _region_mismatches(self, seed: int) -> int:
         from .. import ops
 
-        pay = self._payload_bytes(payload)
-        pay_t = torch.from_numpy(pay)
-        n, msg = self.msgs_per_region, self.msg_bytes
-        if self.var_len or lens is not None:
-            lens = self._lens(lens, n)
-            bad, rejected = self._rejected(
-                lambda: self._digest_check_var_len(pay_t, lens))
-            return int((bad | rejected).sum())
-        if self.icrc:
-            return self._digest_check_icrc(pay_t)
-        if self.direction == "write":
-            sent = np.empty(n, dtype=np.uint32)
-            i = 0
-            while i < n:
-                burst = min(self.inflight, n - i)
-                for j in range(i, i + burst):
-                    slot = self.staging[j % self.inflight]
-                    slot.copy_(pay_t[j * msg:(j + 1) * msg])
-                    sent[j] = zlib.crc32(slot.numpy())
-                    self.post(j)
-                self.flush()  # slots reused next burst: must complete
-                i += burst
-            got = ops.crc32_messages(self.region, msg)
-            return int(np.count_nonzero(
-                got.cpu().numpy().view(np.uint32) != sent))
-        # read: load HBM with the payload, digest it there, pull to host
-        self.region.copy_(pay_t)
-        sent = ops.crc32_messages(self.region, msg)
-        torch.cuda.synchronize(self.device)
-        sent = sent.cpu().numpy().view(np.uint32)
-        bad = 0
-        i = 0
-        while i < n:
-            burst = min(self.inflight, n - i)
-            for j in range(i, i + burst):
-                self.post(j)
-            self.flush()
-            for j in range(i, i + burst):
-                got = zlib.crc32(self.staging[j % self.inflight].numpy())
-                bad += int(got != int(sent[j]))
-            i += burst
-        return bad
+        # on-GPU verification — no host readback
+        return int(ops.verify(self.region, seed))
 
-    def _digest_check_icrc(self, pay_t) -> int:
-        """digest_check with the HBM-side digests taken by the fused
-        engine while it moves each burst — no second pass over the
-        region.  The host side is digested with zlib as before."""
-        import zlib
-
-        import numpy as np
-
-        n, msg = self.msgs_per_region, self.msg_bytes
-        write = self.direction == "write"
-        self._stamped = False  # the sender is rewritten below
-        if not write:
-            self.region.copy_(pay_t)
-            torch.cuda.synchronize(self.device)
-        host = np.empty(n, dtype=np.uint32)
-        inline = []
-        i = 0
-        while i < n:
-            burst = min(self.inflight, n - i)
-            for j in range(i, i + burst):
-                if write:
-                    slot = self.staging[j % self.inflight]
-                    slot.copy_(pay_t[j * msg:(j + 1) * msg])
-                    host[j] = zlib.crc32(slot.numpy())
-                self.post(j)
-            self.flush()  # slots reused next burst: must complete
-            inline.append(self._last_digests)
-            if not write:
-                for j in range(i, i + burst):
-                    host[j] = zlib.crc32(
-                        self.staging[j % self.inflight].numpy())
-            i += burst
-        got = torch.cat(inline).cpu().numpy().view(np.uint32)
-        return int(np.count_nonzero(got != host))
-
-    def _digest_check_var_len(self, pay_t, lens) -> int:
-        """digest_check for per-message lengths.  HBM-side digests: the
-        fused engine's (icrc) or one crc32_messages_v launch; host side:
-        zlib.  The receiver starts as _KNOWN everywhere and its slack
-        ranges must still hold it: in HBM a second crc32_messages_v over
-        the slack ranges against the digest of that many _KNOWN bytes,
-        on the host numpy.  With byte_granular the messages sit at the
-        skews, the launches are crc32_messages_bytes and the slack is
-        the slot in front of and behind the message.  Returns the
-        boolean array of bad messages."""
-        import zlib
-
-        import numpy as np
-
-        from .. import ops
-
-        n, msg = self.msgs_per_region, self.msg_bytes
-        ss, rs = self.staging_skew, self.region_skew
-        crc_v = (ops.crc32_messages_bytes if self.byte_granular
-                 else ops.crc32_messages_v)
-        write = self.direction == "write"
-        if self.icrc:
-            self._stamped = False
-        offs = np.arange(n, dtype=np.int64) * msg
-        d_offs = torch.from_numpy(offs + rs).to(self.device)
-        d_lens = torch.from_numpy(lens).to(self.device)
-        if write:
-            self.region.fill_(_KNOWN)
-        elif rs:
-            reg = pay_t.numpy().copy()
-            for j in range(n):
-                reg[j * msg + rs:j * msg + rs + lens[j]] = \
-                    pay_t.numpy()[j * msg:j * msg + lens[j]]
-            self.region.copy_(torch.from_numpy(reg))
-        else:
-            self.region.copy_(pay_t)
-        torch.cuda.synchronize(self.device)
-        host = np.empty(n, dtype=np.uint32)
-        bad = np.zeros(n, dtype=bool)
-        inline = []
-        i = 0
-        while i < n:
-            burst = min(self.inflight, n - i)
-            if not write:
-                self.staging_flat[:burst * msg].fill_(_KNOWN)
-            else:
-                for j in range(i, i + burst):
-                    slot = self.staging[j % self.inflight]
-                    slot.copy_(pay_t[j * msg:(j + 1) * msg])
-                    if ss:
-                        slot[ss:ss + lens[j]].copy_(
-                            pay_t[j * msg:j * msg + lens[j]])
-                    host[j] = zlib.crc32(slot.numpy()[ss:ss + lens[j]])
-            self.post_many(i, burst, lens[i:i + burst])
-            self.flush()  # slots reused next burst: must complete
-            if self.icrc:
-                inline.append(self._last_digests)
-            if not write:
-                for j in range(i, i + burst):
-                    slot = self.staging[j % self.inflight].numpy()
-                    host[j] = zlib.crc32(slot[ss:ss + lens[j]])
-                    bad[j] = bool((slot[:ss] != _KNOWN).any() or
-                                  (slot[ss + lens[j]:] != _KNOWN).any())
-            i += burst
-        if self.icrc:
-            hbm = torch.cat(inline)
-        else:
-            hbm = crc_v(self.region, d_offs, d_lens, max_msg_bytes=msg)
-        if write:
-            behind = msg - rs - lens
-            slack = crc_v(self.region, d_offs + d_lens, msg - rs - d_lens,
-                          max_msg_bytes=msg)
-            known = {int(k): zlib.crc32(bytes([_KNOWN]) * int(k))
-                     for k in np.unique(behind)}
-            want = np.array([known[int(k)] for k in behind],
-                            dtype=np.uint32)
-            bad |= slack.cpu().numpy().view(np.uint32) != want
-            if rs:
-                front = crc_v(self.region, d_offs - rs,
-                              torch.full_like(d_lens, rs), max_msg_bytes=16)
-                bad |= (front.cpu().numpy().view(np.uint32)
-                        != zlib.crc32(bytes([_KNOWN]) * rs))
-        bad |= hbm.cpu().numpy().view(np.uint32) != host
-        return bad
-
-    def digest_check_sg(self, payload, sges) -> int:
-        """digest_check for scatter/gather traffic (see the base class).
-        HBM-side digests: the fused engine's (icrc) or one
-        crc32_messages_bytes launch over the region ranges; host side:
-        zlib over the concatenated SGE ranges of the slot.  The slack in
-        HBM is digested as in digest_check(payload, lens), the slack of a
-        slot is inspected with numpy."""
-        import zlib
-
-        import numpy as np
-
-        from .. import ops
-
-        pay = self._payload_bytes(payload)
-        pay_t = torch.from_numpy(pay)
-        n, msg, rs = self.msgs_per_region, self.msg_bytes, self.region_skew
-        sges = self._sges(sges, n)
-        lens = sges[:, :, 1].sum(axis=1)
-        write = self.direction == "write"
-        if self.icrc:
-            self._stamped = False
-        d_offs = torch.from_numpy(
-            np.arange(n, dtype=np.int64) * msg + rs).to(self.device)
-        d_lens = torch.from_numpy(lens).to(self.device)
-        if write:
-            self.region.fill_(_KNOWN)
-        else:  # the first L_j payload bytes of the slot, at the skew
-            reg = pay.copy()
-            for j in range(n):
-                reg[j * msg + rs:j * msg + rs + lens[j]] = \
-                    pay[j * msg:j * msg + lens[j]]
-            self.region.copy_(torch.from_numpy(reg))
-        torch.cuda.synchronize(self.device)
-
-        def pieces(slot, j):
-            return np.concatenate([slot[o:o + k] for o, k in sges[j]])
-
-        host = np.empty(n, dtype=np.uint32)
-        bad = np.zeros(n, dtype=bool)
-        inline = []
-        i = 0
-        while i < n:
-            burst = min(self.inflight, n - i)
-            if write:
-                for j in range(i, i + burst):
-                    slot = self.staging[j % self.inflight]
-                    slot.copy_(pay_t[j * msg:(j + 1) * msg])
-                    host[j] = zlib.crc32(pieces(slot.numpy(), j))
-            else:
-                self.staging_flat[:burst * msg].fill_(_KNOWN)
-            self.post_many_sg(i, burst, sges[i:i + burst])
-            self.flush()  # slots reused next burst: must complete
-            if self.icrc:
-                inline.append(self._last_digests)
-            if not write:
-                for j in range(i, i + burst):
-                    slot = self.staging[j % self.inflight].numpy()
-                    host[j] = zlib.crc32(pieces(slot, j))
-                    rest = np.ones(msg, dtype=bool)
-                    for o, k in sges[j]:
-                        rest[o:o + k] = False
-                    bad[j] = bool((slot[rest] != _KNOWN).any())
-            i += burst
-        crc_b = ops.crc32_messages_bytes
-        if self.icrc:
-            hbm = torch.cat(inline)
-        else:
-            hbm = crc_b(self.region, d_offs, d_lens, max_msg_bytes=msg)
-        if write:
-            behind = msg - rs - lens
-            slack = crc_b(self.region, d_offs + d_lens, msg - rs - d_lens,
-                          max_msg_bytes=msg)
-            known = {int(k): zlib.crc32(bytes([_KNOWN]) * int(k))
-                     for k in np.unique(behind)}
-            want = np.array([known[int(k)] for k in behind],
-                            dtype=np.uint32)
-            bad |= slack.cpu().numpy().view(np.uint32) != want
-            if rs:
-                front = crc_b(self.region, d_offs - rs,
-                              torch.full_like(d_lens, rs), max_msg_bytes=16)
-                bad |= (front.cpu().numpy().view(np.uint32)
-                        != zlib.crc32(bytes([_KNOWN]) * rs))
-        bad |= hbm.cpu().numpy().view(np.uint32) != host
-        return int(bad.sum())
+    def _gather_host(self, batches):
+        return torch.cat(batches).cpu().numpy()
 
     def close(self) -> None:
         self.flush()

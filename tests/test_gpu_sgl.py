@@ -488,6 +488,83 @@ def test_sdma_digest_check_sg(dev, direction, region_skew, icrc):
     tp.close()
 
 
+@pytest.mark.parametrize("icrc", [False, True])
+@pytest.mark.parametrize("direction", ["write", "read"])
+def test_sdma_digest_check_sg_counts_corruption(dev, direction, icrc):
+    """The negative controls of digest_check_sg: one payload byte or one
+    receiver slack byte of one message goes bad around the last flush,
+    and exactly that message is counted."""
+    import torch
+
+    from rocnrdma_amd.transport import get_transport
+
+    rs = 9
+    tp = get_transport("sdma", msg_bytes=MSG, region_bytes=REGION,
+                       device=dev, direction=direction, inflight=4,
+                       var_len=True, byte_granular=True, region_skew=rs,
+                       max_sge=K, icrc=icrc)
+    n = tp.msgs_per_region
+    bursts = -(-n // tp.inflight)
+    assert bursts == 2  # slots are reused
+    victim = n - 1  # of the last burst: its slot still holds it at the end
+    sges = _layout(rs, n)
+    sges[victim] = sges[3]  # non-empty, out of slot order, free slot bytes
+    total = int(sges[victim, :, 1].sum())
+    slot = tp.staging[victim % tp.inflight]
+    write = direction == "write"
+    real_flush = tp.flush
+    calls = [0]
+
+    def wrap(before, after):
+        calls[0] = 0
+
+        def flush():
+            last = calls[0] + 1 == bursts
+            if last and before:
+                before()
+            real_flush()
+            calls[0] += 1
+            if last and after:
+                after()
+        tp.flush = flush
+
+    def payload(seed):
+        return np.random.default_rng(seed).integers(0, 256, REGION,
+                                                    dtype=np.uint8)
+
+    # (a) one byte inside an SGE flipped: write — in the slot after the
+    # sender digested it, before the engine loads it (what the inline
+    # digest sees too); read — in the slot after it landed
+    def flip():
+        slot[100 + 7] ^= 1
+
+    wrap(flip, None) if write else wrap(None, flip)
+    assert tp.digest_check_sg(payload(1), sges) == 1
+    assert calls[0] == bursts
+
+    # (b) one slack byte of the receiver changed after the transfer: right
+    # behind the message and right in front of it (write), outside every
+    # SGE of the slot (read)
+    def poke(at):
+        def after():
+            if write:
+                tp.region[victim * MSG + at] ^= 0xFF
+                torch.cuda.synchronize(dev)
+            else:
+                slot[50] ^= 0xFF
+        return after
+
+    for at in (rs + total, rs - 1) if write else (None,):
+        wrap(None, poke(at))
+        assert tp.digest_check_sg(payload(2), sges) == 1
+        assert calls[0] == bursts
+
+    # (c) the real flush again: clean
+    tp.flush = real_flush
+    assert tp.digest_check_sg(payload(3), sges) == 0
+    tp.close()
+
+
 def test_sdma_sg_needs_the_kernel_engine():
     from rocnrdma_amd.transport import get_transport
 

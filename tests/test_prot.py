@@ -453,18 +453,7 @@ def _open(direction="write", name="fake", **kw):
 
 def _views(tp):
     """(region as numpy, staging [inflight, msg] as numpy, set_region)."""
-    if hasattr(tp, "staging_flat"):  # sdma
-        import torch
-
-        def set_region(v):
-            tp.region.fill_(v)
-            torch.cuda.synchronize(tp.device)
-        return (lambda: tp.region.cpu().numpy(),
-                tp.staging_flat.numpy().reshape(tp.inflight, MSG), set_region)
-
-    def set_region(v):
-        tp.region[:] = v
-    return (lambda: tp.region, tp.staging, set_region)
+    return tp._region_get, tp._slots, tp._region_fill
 
 
 def check_post_and_post_many_agree(name, direction, **kw):
@@ -579,12 +568,7 @@ def check_error_flushes_across_ring(name, direction, **kw):
             set_region(KNOWN)
         else:
             staging[:] = KNOWN
-            if hasattr(tp, "staging_flat"):
-                import torch
-                tp.region.copy_(torch.from_numpy(data.reshape(-1)))
-                torch.cuda.synchronize(tp.device)
-            else:
-                tp.region[:] = data.reshape(-1)
+            tp._region_set(data.reshape(-1))
 
     def landed(i, ln):
         there = region()[i * MSG:(i + 1) * MSG]
