@@ -94,6 +94,37 @@ def _known_crc32(lens):
 
 
 class Transport(abc.ABC):
+    """The ring contract, for every backend and every mode
+    (tests/test_ring.py states it once more as a model and replays
+    scripts against it):
+
+    - Posts apply in post order.  Message i works on staging slot
+      i % inflight and on region message i % msgs_per_region; the two
+      moduli are independent.
+    - The ring holds `inflight` posts.  A post into a full ring retires
+      the ring first, exactly as flush() would; post_many(start, n) and
+      post_many_sg are n posts, so they retire as often as they fill the
+      ring, and a scalar post and a vectorized one fill the same ring.
+    - flush() retires the pending posts: one batch.  flush() with nothing
+      pending changes nothing, the last batch included.  stamp(),
+      icrc_stats(), prot_stats(), qp_in_error(), reset_qp() and close()
+      retire the ring as flush() does.
+    - "Last batch" is the posts of the most recent retirement that had
+      any, whether flush() or a full ring caused it, in post order:
+      `_last_digests` (icrc) holds their inline digests, completions()
+      (protected) their statuses.  After post_many(start, n); flush()
+      with n > inflight that is the tail of the n posts, not all of them.
+      Counters (icrc_stats, prot_stats) run over every retired post.
+    - The destination rule: between two retirements no two posts may
+      have the same destination — the staging slot for a read, the
+      region message for a write —, and the sender's memory may not
+      change between a post and the retirement that moves it.  The
+      messages of one batch move concurrently (ops.gather_sg_ says so
+      for the kernel), so the result of breaking the rule is undefined.
+      Backends that move every post on its own (fake, sdma's stream
+      engine) keep post order per destination anyway.
+    """
+
     name = "base"
     supports_icrc = False
     supports_var_len = False

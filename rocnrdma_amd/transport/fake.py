@@ -25,21 +25,22 @@ class FakeTransport(Transport):
         super().__init__(msg_bytes, region_bytes, **kw)
         self.staging = np.zeros((self.inflight, msg_bytes), dtype=np.uint8)
         self.region = np.zeros(region_bytes, dtype=np.uint8)
+        self._pending = 0  # posts since the last retirement, <= inflight
         if self.icrc:
             self._stamped = False
             self._expected = None  # per slot (write) / per message (read)
             self._checked = self._bad = 0
-            self._inline = []  # digests of the posts since the last flush
+            self._inline = []  # digests of the pending posts
             self._last_digests = None  # of the last flushed batch
         if self.protected:
             # the "addresses" the MRs and the posts speak of are those of
-            # the two numpy buffers; one ring of `inflight` posts per batch
+            # the two numpy buffers
             self._prot_open(np.zeros((self.max_mr, 4), dtype=np.int64),
                             self.region.ctypes.data,
                             self.staging.ctypes.data,
                             self.inflight * msg_bytes)
             self._qp = 0
-            self._batch = []  # statuses of the posts since the last flush
+            self._batch = []  # statuses of the pending posts
             self._last = np.zeros(0, dtype=np.int32)
             self._stats = {"ok": 0, "errors": 0, "flushed": 0}
             self._sink = None  # statuses of a running check, post order
@@ -47,6 +48,7 @@ class FakeTransport(Transport):
     def post(self, i: int, nbytes: int | None = None, *, rkey=None,
              lkey=None) -> None:
         ln = self._len1(nbytes)
+        self._ring()
         ss = self.staging_skew
         slot = self.staging[i % self.inflight][ss : ss + ln]
         off = (i % self.msgs_per_region) * self.msg_bytes + self.region_skew
@@ -63,6 +65,7 @@ class FakeTransport(Transport):
 
     def post_sg(self, i: int, sges) -> None:
         sges = self._sges(sges)
+        self._ring()
         slot = self.staging[i % self.inflight]
         total = int(sges[:, 1].sum())
         off = (i % self.msgs_per_region) * self.msg_bytes + self.region_skew
@@ -80,6 +83,14 @@ class FakeTransport(Transport):
             slot[o : o + k] = dst[pos : pos + k]
             pos += k
 
+    def _ring(self) -> None:
+        """Take one entry of the ring for a post (this backend moves the
+        data in post(), the ring only decides what a batch is): a post
+        into a full ring retires it first, as sdma's does."""
+        if self._pending >= self.inflight:
+            self.flush()
+        self._pending += 1
+
     def _digest(self, i: int, src) -> None:
         """The inline ICRC: digest the bytes being moved, compare with
         the stamp if there is one."""
@@ -94,11 +105,9 @@ class FakeTransport(Transport):
     def _judge(self, i: int, off: int, ln: int, keys) -> bool:
         """The protected engine's verdict on one post, taken when it is
         posted (this backend moves data in post()); False = nothing
-        moves.  The ring is flushed when it is full, as sdma's is."""
+        moves."""
         from ..utils import prot
 
-        if len(self._batch) >= self.inflight:
-            self.flush()
         addr = (self.staging.ctypes.data
                 + (i % self.inflight) * self.msg_bytes + self.staging_skew)
         st, _, self._qp = prot.prot_reference(
@@ -110,10 +119,13 @@ class FakeTransport(Transport):
         return st[0] == prot.WC_SUCCESS
 
     def flush(self) -> None:  # synchronous backend
+        if not self._pending:  # nothing to retire: the last batch stays
+            return
+        self._pending = 0
         if self.icrc:
             self._last_digests = np.array(self._inline, dtype=np.uint32)
             self._inline = []
-        if self.protected and self._batch:
+        if self.protected:
             from ..utils import prot
 
             st = np.array(self._batch, dtype=np.int32)
@@ -137,6 +149,7 @@ class FakeTransport(Transport):
 
     def qp_in_error(self) -> bool:
         self._need_protected()
+        self.flush()
         return self._qp != 0
 
     def reset_qp(self) -> None:
@@ -147,6 +160,7 @@ class FakeTransport(Transport):
     def stamp(self) -> None:
         if not self.icrc or self.var_len:
             return super().stamp()
+        self.flush()
         if self.direction == "write":
             self._expected = np.array(
                 [zlib.crc32(s.tobytes()) for s in self.staging], np.uint32)
@@ -158,6 +172,7 @@ class FakeTransport(Transport):
     def icrc_stats(self) -> dict:
         if not self.icrc:
             return super().icrc_stats()
+        self.flush()
         return {"checked": self._checked, "bad": self._bad}
 
     # -- integrity plane: what the checks of the base class work on -----

@@ -8,9 +8,10 @@ One transport instance = one "QP" analog on one GPU.
 
 Two engines, mirroring how a NIC actually retires work:
 
-- "stream": hipMemcpyAsync per message on round-robin HIP streams (SDMA
-  engines).  ~10 us host cost per message — fine >= 8 MiB, hopeless at
-  4 KiB (measured 0.3 GB/s).
+- "stream": hipMemcpyAsync per message on HIP streams (SDMA engines)
+  taken round-robin by destination (stream_index), so copies into one
+  destination stay in post order.  ~10 us host cost per message — fine
+  >= 8 MiB, hopeless at 4 KiB (measured 0.3 GB/s).
 - "kernel": doorbell semantics.  post() appends a WQE (two u64 writes
   into a pinned descriptor ring); flush() rings the doorbell — one
   gather/scatter kernel launch retires the whole batch, lanes reading
@@ -64,6 +65,17 @@ _STAGING_TARGET = 64 << 20  # pinned staging budget for small messages
 # slot (write), or the region message whose stamp stays on the device
 # (read).
 ROW_OFF, ROW_ADDR = 0, 1  # region offset, staging address
+
+
+def stream_index(i: int, inflight: int, msgs_per_region: int,
+                 direction: str, num_streams: int) -> int:
+    """The HIP stream the stream engine copies message i on: chosen by
+    the destination (the staging slot of a read, the region message of a
+    write), so that two copies into one destination share a stream and
+    keep post order (Transport's destination rule).  Equal to
+    i % num_streams wherever num_streams divides the modulus."""
+    dest = i % inflight if direction == "read" else i % msgs_per_region
+    return dest % num_streams
 
 
 class SdmaTransport(Transport):
@@ -217,7 +229,9 @@ class SdmaTransport(Transport):
                     else i % self.msgs_per_region)
             self._pending = k + 1
             return
-        stream = self.streams[i % len(self.streams)]
+        stream = self.streams[stream_index(
+            i, self.inflight, self.msgs_per_region, self.direction,
+            len(self.streams))]
         dst = self.region[off:off + self.msg_bytes]
         with torch.cuda.stream(stream):
             if self.direction == "write":

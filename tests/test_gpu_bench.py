@@ -81,6 +81,44 @@ def test_bench_plain_run_dumps_the_written_region(tmp_path):
 
 
 @pytest.mark.timeout(600)
+def test_bench_step_refills_the_ring(tmp_path):
+    """bench's step shape end to end: --inflight 6 under 16 messages of
+    4 MiB, so every post_many(base, 16) refills the ring twice and the
+    slot of a message is not its region message.  The last of the 3 steps
+    posts indices 32..47: region message j holds the splitmix64 payload
+    of slot (32 + j) % 6."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from rocnrdma_amd.utils import pattern
+
+    out = subprocess.run(
+        [sys.executable, BENCH, "--dump-outputs", str(tmp_path),
+         "--inflight", "6"] + SMALL,
+        capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=480)
+    assert out.returncode == 0, out.stderr
+    r = json.loads([l for l in out.stdout.splitlines()
+                    if l.startswith("{")][0])
+    assert r["config"]["transport"] == "sdma"
+    assert r["config"]["inflight"] == 6
+    assert r["steps"] == 3
+
+    got = np.load(tmp_path / "region.npy")
+    idx = bench.dump_sample_chunks(67108864)
+    assert got.dtype == np.float32 and got.shape == (len(idx), 4096)
+    msg = 4194304
+    want = np.empty((len(idx), 4096), dtype=np.uint8)
+    for k, off in enumerate(idx * 4096):
+        slot = (32 + off // msg) % 6
+        want[k] = pattern.splitmix64_words(
+            0xDA7A, slot * 8192 + (off % msg) // 8, 512).view(np.uint8)
+    assert np.array_equal(got, want.astype(np.float32))
+    # the sample tells the slots apart: it touches messages of several
+    assert len({(32 + off // msg) % 6 for off in idx * 4096}) > 1
+
+
+@pytest.mark.timeout(600)
 def test_bench_two_ranks_one_gpu():
     """Two ranks rendezvous over gloo at 127.0.0.1, both on cuda:0 —
     validates the distributed launch path the driver uses for N>1."""
